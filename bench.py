@@ -24,7 +24,16 @@ rank g's exact per-GPU plan of a P-GPU job with every exchange replaced by a
 device swap of the real message sizes (parallel/comm.py SimCommunicator), for
 a fixed number of sweeps; it reports the per-GPU time per sweep.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 16384]
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--full`` adds what is checked after the timed region: residual and full
+orthogonality of the last solve and, for n <= 8192 or with --check-sigma,
+sigma against the fp64 oracle (the "accuracy" block of the result line).
+``--dump-outputs DIR`` writes what the last timed solve returned as
+DIR/U.npy, DIR/S.npy and DIR/V.npy (sigma whole, in column order; U and V as
+one fixed seeded sample of columns when they are larger than the 64 MB cap),
+so that two builds can be compared output for output on the same input.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 16384] [--full]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 from __future__ import annotations
@@ -219,6 +228,71 @@ def verify_root(res, A, dtype):
     return {"residual_rel": float(r),
             "orth_v_fro": float((V.t() @ V - eye).double().norm()),
             "orth_u_fro": float((U.t() @ U - eye).double().norm())}
+
+
+DUMP_BYTES = 60_000_000  # U and V samples of --dump-outputs together (sigma is whole): < 64 MB
+
+
+def sample_columns(m, n, esize):
+    """Columns of U and V that --dump-outputs keeps: all of them when both
+    matrices fit in DUMP_BYTES, else one fixed seeded choice, ascending."""
+    k = max(1, min(n, DUMP_BYTES // (esize * (m + n))))
+    if k == n:
+        return torch.arange(n)
+    g = torch.Generator().manual_seed(4321)
+    return torch.randperm(n, generator=g)[:k].sort().values
+
+
+def collect_outputs(res, m, n, comm):
+    """What the solve returned, for --dump-outputs: U (m x k), sigma (n, in
+    column order) and V (n x k) on rank 0, k = the sampled columns, fp64 for
+    an fp64 solve and fp32 otherwise.  Columns or rows held by other ranks
+    are summed in (every entry has one owner, the others add zeros)."""
+    if res.S is None:  # gathered output lives on rank 0 only
+        return None
+    out = torch.float64 if res.S.dtype == torch.float64 else torch.float32
+    dev = res.S.device
+    cols = sample_columns(m, n, 8 if out == torch.float64 else 4).to(dev)
+    k = cols.numel()
+    mode = res.info.get("distributed_output")
+
+    def summed(t):
+        if comm.world > 1:
+            t = comm.allreduce_sum_(t.to(comm_device(comm, dev)))
+        return t
+
+    if mode is True:  # column slots: rows of At / Vt / S (verify_distributed)
+        loc, glob = _global_columns(res, n, comm)
+        loc = torch.tensor(loc, device=dev, dtype=torch.long)
+        glob = torch.tensor(glob, device=dev, dtype=torch.long)
+        where = torch.full((n,), -1, device=dev, dtype=torch.long)
+        where[cols] = torch.arange(k, device=dev)
+        pos = where[glob]
+        keep = pos >= 0
+        Ut = torch.zeros(k, m, dtype=out, device=dev)
+        Vt = torch.zeros(k, n, dtype=out, device=dev)
+        S = torch.zeros(n, dtype=out, device=dev)
+        Ut[pos[keep]] = res.U[loc[keep], :m].to(out)
+        Vt[pos[keep]] = res.V[loc[keep], :n].to(out)
+        S[glob] = res.S[loc].to(out)
+        U, S, V = summed(Ut).t(), summed(S), summed(Vt).t()
+    elif mode == "rows":  # QR path: U is this rank's row block, sigma and V complete
+        r0, r1 = res.info["u_rows"]
+        U = torch.zeros(m, k, dtype=out, device=dev)
+        U[r0:r1] = res.U[:, cols].to(out)
+        U, S, V = summed(U), res.S.to(out), res.V[:, cols].to(out)
+    elif comm.rank == 0:  # complete on rank 0
+        U, S, V = res.U[:, cols].to(out), res.S.to(out), res.V[:, cols].to(out)
+    if comm.rank != 0:
+        return None
+    return {"U": U, "S": S, "V": V}
+
+
+def dump_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().contiguous().numpy())
 
 
 def make_generator(m, dev, work, dtype):
@@ -467,13 +541,18 @@ def run_native(a, dtype, work):
         el = float(t[0])
     flops = sum(algorithmic_flops_per_sweep(m, n) * s_ for s_ in sweeps)
     acc = None
-    if not a.no_verify:
-        class _Res:
-            pass
-        res = _Res()
-        res.U, res.V, res.S = At, Vt, S
-        res.info = {"geometry": {"B": B}, "held": [int(p.held[0]), int(p.held[1])],
-                    "distributed_output": True}
+
+    class _Res:
+        pass
+    res = _Res()
+    res.U, res.V, res.S = At, Vt, S
+    res.info = {"geometry": {"B": B}, "held": [int(p.held[0]), int(p.held[1])],
+                "distributed_output": True}
+    if a.dump_outputs:
+        arrays = collect_outputs(res, m, n, comm)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, arrays)
+    if a.full and not a.no_verify:
         acc = verify_distributed(res, gen, m, n, comm, work)
         if want_sigma(a, n):
             err = sigma_check(res, gen, m, n, comm)
@@ -616,12 +695,20 @@ def main():
                    help="distributed executor: torch.distributed + Python issue (python), or "
                         "the C++ solver libsvdj_dist with RCCL called directly (native)")
     p.add_argument("--json-out", default=None)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also check the last solve: residual, full "
+                        "orthogonality and (n <= 8192 or --check-sigma) sigma against the fp64 "
+                        "oracle, reported as the accuracy block; a plain run only times")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write U, sigma and V of the last timed solve as DIR/U.npy, DIR/S.npy, "
+                        "DIR/V.npy (a fixed seeded sample of the columns of U and V above 64 MB)")
     p.add_argument("--no-verify", action="store_true",
-                   help="skip the post-timing accuracy check")
+                   help="with --full: skip the post-timing accuracy check")
     p.add_argument("--check-sigma", action="store_true",
-                   help="compare sigma with an fp64 oracle (svdvals) even when n > 8192")
+                   help="with --full: compare sigma with an fp64 oracle (svdvals) even when "
+                        "n > 8192")
     p.add_argument("--no-sigma-check", action="store_true",
-                   help="skip the sigma check that runs by default for n <= 8192")
+                   help="with --full: skip the sigma check that runs by default for n <= 8192")
     a = p.parse_args()
 
     import svdj
@@ -700,7 +787,12 @@ def main():
     ms = elapsed / a.steps * 1e3
     geo = last.info["geometry"]
     acc = None
-    if not a.no_verify:
+    if a.dump_outputs:
+        arrays = collect_outputs(last, m, n, comm)
+        if comm.rank == 0:
+            dump_outputs(a.dump_outputs, arrays)
+    verify = a.full and not a.no_verify
+    if verify:
         if a.root_owned:
             acc = verify_root(last, A_root, work) if comm.rank == 0 else None
         elif last.info.get("precondition") == "qr":
@@ -709,7 +801,7 @@ def main():
             acc = verify_distributed(last, gen, m, n, comm, work)
     # sigma vs the fp64 oracle; on the QR path sigma is complete on every rank
     # (the oracle is svdvals of the whole m x n A)
-    if not a.no_verify and want_sigma(a, n):
+    if verify and want_sigma(a, n):
         if a.root_owned:
             err = None
             if comm.rank == 0:

@@ -125,7 +125,8 @@ def test_bench_native_engine_matches_python_engine(tmp_path):
     for eng in ("native", "python"):
         js = tmp_path / f"{eng}.json"
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", eng,
-                            "--size", "1024", "--steps", "1", "--warmup", "0", "--json-out", str(js)],
+                            "--size", "1024", "--steps", "1", "--warmup", "0", "--full",
+                            "--json-out", str(js)],
                            capture_output=True, text=True, timeout=300,
                            env=dict(os.environ, MASTER_PORT=str(29950 + len(out))))
         assert r.returncode == 0, r.stderr[-2000:]

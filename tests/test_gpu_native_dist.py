@@ -162,7 +162,7 @@ def test_native_engine_production_default_matches_python(tmp_path):
     for eng in ("native", "python"):
         js = tmp_path / f"{eng}.json"
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", eng,
-                            "--steps", "1", "--warmup", "1", "--json-out", str(js)],
+                            "--steps", "1", "--warmup", "1", "--full", "--json-out", str(js)],
                            capture_output=True, text=True, timeout=240,
                            env=dict(os.environ, MASTER_PORT=str(29960 + len(out))))
         assert r.returncode == 0, r.stderr[-2000:]

@@ -27,7 +27,7 @@ for v in "$@"; do
   i=$((i+1))
   k=${v%%@*}; x=""; [ "$k" != "$v" ] && x=${v#*@}
   if [ "$k" = "-" ]; then unset SVDJ_DEBUG; else export SVDJ_DEBUG="$k"; fi
-  timeout -k 10 400 python3 -u $R/bench.py --n ${N:-16384} --steps 1 --warmup 0 $x \
+  timeout -k 10 400 python3 -u $R/bench.py --n ${N:-16384} --steps 1 --warmup 0 --full $x \
     > $O/acc_${i}.log 2>&1 || { tail -20 $O/acc_${i}.log; exit 1; }
   tail -1 $O/acc_${i}.log | python3 -c "$summ" "$v/acc"
 done

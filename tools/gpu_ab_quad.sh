@@ -27,7 +27,7 @@ import csv, sys
 for x in list(csv.DictReader(open(sys.argv[1])))[:8]:
     print("  %-44s %6s %9.1f ms %8.1f us" % (x['Name'][:44], x['Calls'], float(x['TotalDurationNs'])/1e6, float(x['AverageNs'])/1e3))
 PY
-  timeout -k 10 300 python3 -u $R/bench.py --n 16384 --steps 2 --warmup 1 > $O/bench_$v.log 2>&1 \
+  timeout -k 10 300 python3 -u $R/bench.py --n 16384 --steps 2 --warmup 1 --full > $O/bench_$v.log 2>&1 \
     || { tail -20 $O/bench_$v.log; exit 1; }
   tail -1 $O/bench_$v.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['sweeps'], d['accuracy'])"
 done

@@ -34,19 +34,19 @@ PY
 }
 for set in "$@"; do
   case $set in
-    headline) b headline16384 400 --steps 3 --warmup 1 ;;
+    headline) b headline16384 400 --full --steps 3 --warmup 1 ;;
     sigma)
-      b sigma4096 200 --n 4096 --steps 3 --warmup 1 --check-sigma
-      b sigma8192 300 --n 8192 --steps 2 --warmup 1 --check-sigma
-      b sigma16384 600 --n 16384 --steps 1 --warmup 0 --check-sigma --progress ;;
+      b sigma4096 200 --full --n 4096 --steps 3 --warmup 1 --check-sigma
+      b sigma8192 300 --full --n 8192 --steps 2 --warmup 1 --check-sigma
+      b sigma16384 600 --full --n 16384 --steps 1 --warmup 0 --check-sigma --progress ;;
     configs)
-      b tall_fp32 300 --m 32768 --n 8192 --steps 3 --warmup 1
-      b tall_bf16 300 --m 32768 --n 8192 --dtype bf16 --steps 3 --warmup 1
-      b f64_10000 300 --n 10000 --dtype fp64 --steps 2 --warmup 1 ;;
+      b tall_fp32 300 --full --m 32768 --n 8192 --steps 3 --warmup 1
+      b tall_bf16 300 --full --m 32768 --n 8192 --dtype bf16 --steps 3 --warmup 1
+      b f64_10000 300 --full --n 10000 --dtype fp64 --steps 2 --warmup 1 ;;
     fp64ref)
-      b f64_5000 200 --n 5000 --dtype fp64 --steps 3 --warmup 1
-      b f64_20000 600 --n 20000 --dtype fp64 --steps 1 --warmup 0 --progress
-      b f64_30000 1000 --n 30000 --dtype fp64 --steps 1 --warmup 0 --progress ;;
+      b f64_5000 200 --full --n 5000 --dtype fp64 --steps 3 --warmup 1
+      b f64_20000 600 --full --n 20000 --dtype fp64 --steps 1 --warmup 0 --progress
+      b f64_30000 1000 --full --n 30000 --dtype fp64 --steps 1 --warmup 0 --progress ;;
     big) b big65536 1100 --n 65536 --steps 1 --warmup 0 --progress ;;
     sims)
       for P in 8 4 2 1; do b sim$P 300 --simulate-P $P --n 16384 --sim-sweeps 3; done

@@ -6,9 +6,9 @@ O=$R/gpurun_out/final6
 mkdir -p $O
 export SVDJ_NO_AUTOBUILD=1
 cd $R
-timeout -k 10 600 python3 -u bench.py > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
+timeout -k 10 600 python3 -u bench.py --full > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
 tail -1 $O/bench_default.log | cut -c1-300
-timeout -k 10 300 python3 -u bench.py --n 4096 --steps 10 --warmup 2 > $O/bench_4096.log 2>&1 || { tail -20 $O/bench_4096.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --n 4096 --steps 10 --warmup 2 --full > $O/bench_4096.log 2>&1 || { tail -20 $O/bench_4096.log; exit 1; }
 tail -1 $O/bench_4096.log | cut -c1-200
 timeout -k 10 300 python3 -u tools/svd_api_time.py --n 16384 --reps 2 --engines pipeline > $O/svd_api.jsonl 2>&1 || { tail -20 $O/svd_api.jsonl; exit 1; }
 cat $O/svd_api.jsonl

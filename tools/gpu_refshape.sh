@@ -14,7 +14,7 @@ export SVDJ_SHARED_GPU=1
 for n in 5000 10000; do
   timeout -k 10 400 python -m torch.distributed.run --nnodes 1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port $((29600 + n / 1000)) bench.py --gpus 2 --size $n \
-    --dtype fp64 --root-owned --steps 1 --warmup 1 --json-out $O/root_p2_fp64_$n.json \
+    --dtype fp64 --root-owned --steps 1 --warmup 1 --full --json-out $O/root_p2_fp64_$n.json \
     > $O/root_p2_fp64_$n.log 2>&1 || { tail -20 $O/root_p2_fp64_$n.log; exit 1; }
   tail -1 $O/root_p2_fp64_$n.log | cut -c1-160
 done

@@ -18,7 +18,7 @@ for N in 1 2 4 8; do
     CMD=(python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1
          --master-port "$PORT" bench.py --gpus "$N")
   fi
-  SVDJ_COMM_TIMEOUT=${SVDJ_COMM_TIMEOUT:-300} timeout -k 10 1200 "${CMD[@]}" --json-out "$OUT/scale_n$N.json" "$@" \
+  SVDJ_COMM_TIMEOUT=${SVDJ_COMM_TIMEOUT:-300} timeout -k 10 1200 "${CMD[@]}" --json-out "$OUT/scale_n$N.json" --full "$@" \
     > "$OUT/scale_n$N.log" 2>&1 || { echo "N=$N failed"; tail -20 "$OUT/scale_n$N.log"; exit 1; }
   tail -1 "$OUT/scale_n$N.log"
 done
