@@ -3372,6 +3372,47 @@ extern "C" int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* 
   return 0;
 }
 
+// The quad step's apply alone (tests / kernel A/B): [a b c d] <- [a b c d] T
+// on A (m_pad rows) and V (n_v rows, or NULL) for the nq quads of `pairs`
+// (2 nq pairs in quad order (a,c),(b,d)), T - I given split into np bf16
+// parts in the ts_frag layout; skip1 / skip2 (2 nq flags each): a quad is
+// skipped when all four of its flags are set.  apply_quad_ts_kernel<np> on
+// `grid` workgroups, launched as launch_apply does; cheap_tol = 2^-cheap_log2;
+// work (device uint32[2], or NULL): the kernel's work counters, accumulated.
+extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, int ldv,
+                               const int32_t* pairs, int nq, const void* Ts,
+                               const int32_t* skip1, const int32_t* skip2, int np, int grid,
+                               int cheap_log2, uint32_t* work, void* stream) {
+  int rc = check_dims(m_pad, lda, V, n_v, ldv, 0);
+  if (rc) return rc;
+  if (lda % 4 || (V && ldv % 4)) {  // the tile DMA moves 16 bytes per lane
+    set_error("svdj_apply_quad: lda/ldv %d/%d must be multiples of 4", lda, ldv);
+    return -2;
+  }
+  if ((np != 2 && np != 3) || grid < 1 || nq < 1 || cheap_log2 < 0 || cheap_log2 > 126 || !A ||
+      !pairs || !Ts || !skip1 || !skip2) {
+    set_error("svdj_apply_quad: bad np/grid/nq/cheap_log2 %d/%d/%d/%d or a null pointer", np, grid,
+              nq, cheap_log2);
+    return -2;
+  }
+  const int at = m_pad / 32, vt = V ? n_v / 32 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (np == 3)
+    hipLaunchKernelGGL((apply_quad_ts_kernel<3>), dim3(grid), dim3(kQuadTsThreads), 0, st,
+                       (float*)A, lda, at, (float*)V, ldv, vt, pairs, nq, (const bf16x8*)Ts, skip1,
+                       skip2, work, ldexpf(1.0f, -cheap_log2));
+  else
+    hipLaunchKernelGGL((apply_quad_ts_kernel<2>), dim3(grid), dim3(kQuadTsThreads), 0, st,
+                       (float*)A, lda, at, (float*)V, ldv, vt, pairs, nq, (const bf16x8*)Ts, skip1,
+                       skip2, work);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("svdj_apply_quad launch: %s", hipGetErrorString(e));
+    return -101;
+  }
+  return 0;
+}
+
 // Test/diagnostic hook: X <- X Q for ONE column-block pair (blocks 0 and 1 of
 // X, 2W columns with leading dimension ld, rows padded to SVDJ_ROW_ALIGN),
 // Q row-major 2W x 2W on the device, with the given matrix-core mode.
@@ -3414,7 +3455,7 @@ extern "C" int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld
                        rows_chunk, rows, (double*)nullptr, 0, 0, 0, dbuf, (const double*)Q,
                        dbuf + 2);
   else if (dtype == 1 && mma == 0 && W == 64)
-    hipLaunchKernelGGL((apply_kernel<double, 64>), grid, blk, 0, st, (double*)X, ld, chunks,
+    hipLaunchKernelGGL((apply_kernel<double, 64>), grid, dim3(apply_threads<double, 64>()), 0, st, (double*)X, ld, chunks,
                        rows_chunk, rows, (double*)nullptr, 0, 0, 0, dbuf, (const double*)Q,
                        dbuf + 2);
   else {

@@ -120,6 +120,30 @@ int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* pairs, int 
 // ld, `rows` a multiple of SVDJ_ROW_ALIGN), Q row-major 2W x 2W on the
 // device, with matrix-core mode `mma` (as svdj_block_steps).
 int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld, const void* Q, void* stream);
+// The quad step's apply alone (fp32, W = 64): [a b c d] <- [a b c d] T in
+// place on A (m_pad rows) and V (n_v rows; NULL: A only) for each of the nq
+// quads, launched as a quad step of svdj_block_steps launches it.
+//   pairs   device int32 [2 nq][2], quad order: (a,c), (b,d) per quad
+//   Ts      device bf16: T - I of every quad (T rounded to fp32 first) split
+//           into np round-to-nearest-even bf16 parts, part p of
+//           (T - I)[32 kb + 8 g + e][32 ct + 16 cs + i] at
+//           [q][kb][ct][cs][p][lane = 16 g + i][e]  (q < nq; kb, ct < 8; cs < 2;
+//           g < 4; i < 16; e < 8)
+//   skip1, skip2  device int32 [2 nq] each: quad q is skipped (its columns
+//           untouched, its Ts never read) when its four flags are all nonzero
+//   np      2 or 3 parts (mma 2 / 1 of svdj_block_steps)
+//   grid    workgroups of the persistent kernel, >= 1 (256; 192 / 224 next to
+//           a second chain)
+//   cheap_log2  np = 3: a 128-row half of a 32-column tile of T - I whose
+//           largest part 0 is <= 2^-cheap_log2 takes the first-order form
+//           (production: 7; 126: never)
+//   work    device uint32[2] or NULL, accumulated: [0] MFMAs issued / 24,
+//           [1] 32-row tiles moved (metric words 6, 7 of svdj_stop.h)
+// lda, ldv multiples of 4.  Returns < 0 with the error string set, nothing
+// launched, on a bad argument.
+int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, int ldv, const int32_t* pairs,
+                    int nq, const void* Ts, const int32_t* skip1, const int32_t* skip2, int np,
+                    int grid, int cheap_log2, uint32_t* work, void* stream);
 
 // ---------------------------------------------------------------------------
 // Post-processing / utilities.

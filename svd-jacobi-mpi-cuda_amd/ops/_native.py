@@ -128,6 +128,9 @@ def hip_lib():
              [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p])
         _sig(lib, "svdj_apply_q", c_int,
              [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p])
+        _sig(lib, "svdj_apply_quad", c_int,
+             [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+              c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])
         _sig(lib, "svdj_set_identity", c_int,
              [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
         _sig(lib, "svdj_col_norms2", c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])

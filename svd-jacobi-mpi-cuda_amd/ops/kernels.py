@@ -414,6 +414,49 @@ def apply_q(Xt: torch.Tensor, Q: torch.Tensor, W: int, mma="native"):
                                      rows, Xt.stride(0), _ptr(Q), _stream(Xt)), "apply_q")
 
 
+def apply_quad(At, Vt, m_pad, pairs, Ts, skip1, skip2, np: int = 3, grid: int = 256,
+               cheap_log2: int = 7, work: torch.Tensor | None = None):
+    """The quad step's apply alone (fp32, W = 64; csrc/hip/block.hip
+    apply_quad_ts_kernel, launched as a quad step launches it): in place
+    [a b c d] <- [a b c d] T on At (rows [0, m_pad)) and Vt (all n_v rows, or
+    None) for the quads of ``pairs`` (2 nq, 2) in quad order ((a, c), (b, d)).
+    ``Ts``: bfloat16, nq * 256 * 256 * np elements, T - I split into ``np``
+    parts in the kernel's fragment layout (svdj_hip.h svdj_apply_quad);
+    ``skip1`` / ``skip2``: int32 (2 nq,) flags, a quad with all four set is
+    skipped.  ``work``: int32 (2,) device tensor the kernel's work counters
+    are added to (see :func:`metric_work`), or None."""
+    _check_layout(At, m_pad)
+    if At.dtype != torch.float32 or not At.is_cuda:
+        raise ValueError("apply_quad: fp32 device data")
+    dev = At.device
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] % 2 or pairs.shape[0] == 0:
+        raise ValueError("apply_quad: pairs must be (2 nq, 2), nq >= 1")
+    nq = pairs.shape[0] // 2
+    hp = pairs.cpu()
+    nb = min(At.shape[0], Vt.shape[0] if Vt is not None else At.shape[0]) // 64
+    if int(hp.min()) < 0 or int(hp.max()) >= nb:
+        raise ValueError(f"apply_quad: block index outside [0, {nb})")
+    pairs = pairs.to(torch.int32).contiguous().to(dev)
+    n_v = ldv = 0
+    if Vt is not None:
+        if Vt.dtype != torch.float32 or Vt.device != dev or Vt.dim() != 2 or Vt.stride(1) != 1:
+            raise ValueError("apply_quad: Vt must be an fp32 (ncols, ldv) tensor on At's device")
+        n_v, ldv = Vt.shape[1], Vt.stride(0)
+    if (Ts.dtype != torch.bfloat16 or Ts.device != dev or not Ts.is_contiguous()
+            or Ts.numel() != nq * 256 * 256 * int(np)):
+        raise ValueError("apply_quad: Ts must be contiguous bfloat16 with nq * 256 * 256 * np elements")
+    for sk in (skip1, skip2):
+        if sk.dtype != torch.int32 or sk.device != dev or not sk.is_contiguous() or sk.numel() != 2 * nq:
+            raise ValueError("apply_quad: skip flags must be contiguous int32 (2 nq,) on At's device")
+    if work is not None and (work.dtype != torch.int32 or work.device != dev
+                             or not work.is_contiguous() or work.numel() < 2):
+        raise ValueError("apply_quad: work must be a contiguous int32 (2,) tensor on At's device")
+    hip_check(hip_lib().svdj_apply_quad(_ptr(At), At.stride(0), m_pad, _ptr(Vt), n_v, ldv,
+                                        _ptr(pairs), nq, _ptr(Ts), _ptr(skip1), _ptr(skip2),
+                                        int(np), int(grid), int(cheap_log2), _ptr(work),
+                                        _stream(At)), "apply_quad")
+
+
 def block_solve(At, Vt, D, m_pad, W, tol, max_inner, max_sweeps, mma="native",
                 tol_mode="relative", inner_order="cyclic", stop_rule="second_order"):
     """Single-device block Jacobi (round-robin over ncols/W blocks, first
@@ -461,6 +504,6 @@ __all__ = [
     "METRIC_WORDS", "read_stop", "metric_stop_values", "metric_work", "sweep_converged", "STOP_RULES",
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
     "block_workspace", "block_steps", "block_solve", "check_block", "MMA_CODES", "mma_code",
-    "apply_q",
+    "apply_q", "apply_quad",
     "gram_cross", "gram_quad",
 ]

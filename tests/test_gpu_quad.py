@@ -296,3 +296,136 @@ def test_block_step_many_pairs_matches_few_pairs(svdj, cuda, dtype):
         R.block_step(At64, Vt64, D64, pairs[0], W, False, tol, 1, order="cross")
         torch.testing.assert_close(a1[:, :m], At64[:, :m], rtol=1e-11, atol=1e-11)
         torch.testing.assert_close(v1, Vt64, rtol=1e-11, atol=1e-11)
+
+
+# ---- quad steps late in a solve, next to a second chain, on the 2-part Gram,
+# and with converged and coupled quads in one step (the apply kernel alone:
+# tests/test_gpu_apply.py)
+def _quad_members(pairs0):
+    """(nq, 4) blocks of every quad in [a b c d] order."""
+    p = pairs0.long().view(-1, 2, 2)
+    return torch.stack([p[:, 0, 0], p[:, 1, 0], p[:, 0, 1], p[:, 1, 1]], 1)
+
+
+def _late_sweep_input(svdj, nb, m, m_pad, eps, seed=11):
+    """A = A0 (I + eps E): in A0 the 256 columns of every quad are orthogonal
+    with well separated norms (logspace(0, 1), shuffled: _orth_blocks' close
+    norms turn any coupling into a large angle), E has entries in [-0.5, 0.5];
+    the rotation angles are about 60 eps.  Returns At fp64 (nb*64, m_pad)."""
+    W = 64
+    A0 = _orth_blocks(nb, W, m, m_pad, seed=seed)
+    for q, mem in enumerate(_quad_members(_quad_pairs(svdj, nb)[0])):
+        cols = (mem[:, None] * W + torch.arange(W)).reshape(-1)
+        g = torch.Generator().manual_seed(100 + q)
+        nr = torch.logspace(0, 1, 4 * W, dtype=torch.float64)[torch.randperm(4 * W, generator=g)]
+        qq, _ = torch.linalg.qr(A0[cols, :m].t())
+        A0[cols, :m] = (qq * nr).t()
+    g = torch.Generator().manual_seed(17)
+    E = torch.rand(nb * W, nb * W, generator=g, dtype=torch.float64) - 0.5
+    return (A0 + eps * E.t() @ A0).float().double()
+
+
+def _run_quad_step(svdj, cuda, A64, nb, m_pad, tol=1e-6, **kw):
+    K = svdj.ops.kernels
+    At = A64.float().to(cuda)
+    Vt = torch.zeros(nb * 64, nb * 64, dtype=torch.float32, device=cuda)
+    K.set_identity(Vt, nb * 64)
+    D = K.col_norms2(At, m_pad)
+    metric = K.new_metric(cuda)
+    K.block_steps(At, Vt, D, m_pad, _quad_pairs(svdj, nb).to(cuda), 64, [4, 5], tol, 1, metric,
+                  mma="bf16x6", **kw)
+    return At.cpu(), Vt.cpu(), D.cpu(), metric  # (the device metric: read_metric decodes it)
+
+
+@pytest.mark.parametrize("eps", [3e-4, 2.5e-5])
+def test_quad_step_late_sweep(svdj, cuda, eps):
+    """A quad step on nearly converged data (rotation angles ~0.02 and ~1e-3):
+    rotation count and convergence value of ops.reference.quad_step, A, V, D
+    to 2e-4, V orthogonal, A = A0 V -- and the apply's first-order k halves
+    ran: fewer than 4 MFMA units per tile and wave.  Also next to a second
+    chain (shared_gpu: the apply on 192 workgroups): bitwise the same."""
+    K, R = svdj.ops.kernels, svdj.ops.reference
+    W, nb, m, m_pad = 64, 8, 500, 512
+    n = nb * W
+    A64 = _late_sweep_input(svdj, nb, m, m_pad, eps)
+    At, Vt, D, metric = _run_quad_step(svdj, cuda, A64, nb, m_pad)
+    At64, Vt64 = A64.clone(), torch.eye(n, dtype=torch.float64)
+    D64 = (At64 ** 2).sum(1)
+    pairs = _quad_pairs(svdj, nb)
+    mx_ref, nrot_ref = R.quad_step(At64, Vt64, D64, pairs[0], pairs[1], W, 1e-6, 1)
+    mx, nrot = K.read_metric(metric)
+    assert nrot == nrot_ref == nb
+    assert math.isclose(mx, mx_ref, rel_tol=1e-3)
+    rt = 2e-4
+    torch.testing.assert_close(At.double()[:, :m], At64[:, :m], rtol=rt, atol=rt)
+    torch.testing.assert_close(Vt.double(), Vt64, rtol=rt, atol=rt)
+    torch.testing.assert_close(D.double(), D64, rtol=rt, atol=rt)
+    v = Vt.double()
+    assert float((v @ v.t() - torch.eye(n, dtype=torch.float64)).abs().max()) < 2e-6
+    assert float((A64[:, :m].t() @ v.t() - At.double()[:, :m].t()).abs().max()) < 2e-5
+    work = K.metric_work(metric)
+    print("late sweep: MFMA units per tile and wave", float(work[0] / (8 * work[1])))
+    assert work[1] == (nb // 4) * (m_pad + n) // 32 and work[0] < 4 * 8 * work[1]
+    At2, Vt2, D2, metric2 = _run_quad_step(svdj, cuda, A64, nb, m_pad, shared_gpu=True)
+    assert torch.equal(At2, At) and torch.equal(Vt2, Vt) and torch.equal(D2, D)
+    assert torch.equal(metric2, metric)
+
+
+def test_quad_step_shared_gpu_bitwise(svdj, cuda):
+    """mma bit 9 (another chain on the GPU: the quad apply on 192 workgroups)
+    changes no bit of A, V, D or the metric."""
+    nb, m, m_pad = 16, 700, 768
+    A64 = _orth_blocks(nb, 64, m, m_pad, seed=3)
+    a1, v1, d1, m1 = _run_quad_step(svdj, cuda, A64, nb, m_pad)
+    a2, v2, d2, m2 = _run_quad_step(svdj, cuda, A64, nb, m_pad, shared_gpu=True)
+    assert svdj.ops.kernels.read_metric(m1)[1] == nb
+    assert torch.equal(a1, a2) and torch.equal(v1, v2) and torch.equal(d1, d2)
+    assert torch.equal(m1, m2)
+
+
+def test_quad_step_two_part_gram(svdj, cuda):
+    """mma bit 8 through block_steps (the quad Gram on 2 bf16 parts steers
+    only the angles): every pair rotates, V stays orthogonal and A = A0 V."""
+    nb, m, m_pad = 16, 700, 768
+    n = nb * 64
+    A64 = _orth_blocks(nb, 64, m, m_pad, seed=3)
+    a, v, d, met = _run_quad_step(svdj, cuda, A64, nb, m_pad, gram_parts=2)
+    a3, v3, d3, met3 = _run_quad_step(svdj, cuda, A64, nb, m_pad)
+    assert svdj.ops.kernels.read_metric(met)[1] == svdj.ops.kernels.read_metric(met3)[1] == nb
+    assert not torch.equal(a, a3)  # the 2-part Gram did run
+    v = v.double()
+    assert float((v @ v.t() - torch.eye(n, dtype=torch.float64)).abs().max()) < 2e-6
+    assert float((A64[:, :m].t() @ v.t() - a.double()[:, :m].t()).abs().max()) < 2e-5
+
+
+def test_quad_step_mixed_converged_and_coupled(svdj, cuda):
+    """4 quads in a step, two of them orthonormal 256-column panels: the
+    reference's rotated-pair count, and the converged quads' A, V, D bitwise
+    unchanged (the apply's lookup of the active quads between skipped ones)."""
+    K, R = svdj.ops.kernels, svdj.ops.reference
+    W, nb, m, m_pad = 64, 16, 700, 768
+    A64 = _orth_blocks(nb, W, m, m_pad, seed=3)
+    pairs = _quad_pairs(svdj, nb)
+    mem = _quad_members(pairs[0])
+    done = [0, 2]
+    still = []
+    for q in done:
+        cols = (mem[q][:, None] * W + torch.arange(W)).reshape(-1)
+        g = torch.Generator().manual_seed(300 + q)
+        qq, _ = torch.linalg.qr(torch.rand(m, 4 * W, generator=g, dtype=torch.float64))
+        A64[cols, :m] = qq.t()
+        still.append(cols)
+    still = torch.cat(still)
+    A64 = A64.float().double()
+    At0 = A64.float()
+    D0 = K.col_norms2(At0.to(cuda), m_pad).cpu()
+    At, Vt, D, metric = _run_quad_step(svdj, cuda, A64, nb, m_pad, tol=1e-3)
+    At64, Vt64 = A64.clone(), torch.eye(nb * W, dtype=torch.float64)
+    D64 = D0.double()
+    _, nrot_ref = R.quad_step(At64, Vt64, D64, pairs[0], pairs[1], W, 1e-3, 1)
+    assert K.read_metric(metric)[1] == nrot_ref == 8
+    assert torch.equal(At[still], At0[still]) and torch.equal(D[still], D0[still])
+    assert torch.equal(Vt[still], torch.eye(nb * W)[still])
+    moved = torch.ones(nb * W, dtype=torch.bool)
+    moved[still] = False
+    assert not torch.equal(At[moved], At0[moved])
