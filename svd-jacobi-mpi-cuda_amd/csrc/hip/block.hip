@@ -2168,8 +2168,9 @@ __global__ __launch_bounds__(NT) void quad_update_kernel(
 // extra lane offsets took from the T slice.)
 // Work: the active quads (some step-s or step-(s+1) pair rotated) are listed
 // by every wave with ballots over the skip flags (no extra launch, no host
-// sync); their tiles, flattened, are dealt to the persistent grid in equal
-// contiguous ranges (one workgroup per CU: the LDS is 160 KB).
+// sync); their tiles, flattened, are dealt to the persistent grid in
+// contiguous ranges of equal cost (one workgroup per CU: the LDS is 160 KB).
+// Inside a quad, what T leaves unchanged is skipped (SPARSE in the kernel).
 constexpr int kQuadTsThreads = 512;
 constexpr int kQuadTsGrid = 256;
 // While the other chain's latency-bound kernels (Gram, EVDs, Q builds, update)
@@ -2188,6 +2189,23 @@ struct QuadTsLds {
   static constexpr int TOTAL = 2 * S_BYTES + 2 * R_BYTES;
 };
 static_assert(QuadTsLds<3>::TOTAL <= 163840, "T-stationary quad apply LDS");
+
+// s_waitcnt vmcnt(n rounded down to even), n <= 20 (wave-uniform n)
+__device__ __forceinline__ void wait_vmcnt_upto(int n) {
+  switch (n >> 1) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
+    case 7: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
+    case 9: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
+  }
+}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -2222,18 +2240,62 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
     if (q >= nq) return false;
     return (skip1[2 * q] & skip1[2 * q + 1] & skip2[2 * q] & skip2[2 * q + 1]) == 0;
   };
-  int nact = 0;
-  for (int b0 = 0; b0 < nq; b0 += SVDJ_WAVE) nact += __popcll(__ballot(active(b0 + lane)));
+  // Cost of a quad's tile, 1 .. 4: the column blocks of [a b c d] its flags say
+  // can change (a: (a,c) or (a,d) rotated, b: (b,d) or (b,c), c: (a,c) or
+  // (b,c), d: (b,d) or (a,d)) -- about the blocks the tile moves, see SPARSE
+  // below.  Only the deal uses it: what is skipped is decided from T's values.
+  auto cost = [&](int q) -> int {
+    if (q >= nq) return 1;
+    const int ac = skip1[2 * q] == 0, bd = skip1[2 * q + 1] == 0;
+    const int ad = skip2[2 * q] == 0, bc = skip2[2 * q + 1] == 0;
+    const int w = (ac | ad) + (bd | bc) + (ac | bc) + (bd | ad);
+    return w < 1 ? 1 : w;
+  };
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int nact = 0, wsum = 0;
+  for (int b0 = 0; b0 < nq; b0 += SVDJ_WAVE) {
+    const bool a = active(b0 + lane);
+    const int w1 = cost(b0 + lane) - 1;
+    const int n = __popcll(__ballot(a));
+    nact += n;
+    wsum += n + __popcll(__ballot(a && (w1 & 1))) + 2 * __popcll(__ballot(a && (w1 & 2)));
+  }
   if (nact == 0) return;
   const int G = (int)gridDim.x, nt = a_tiles + v_tiles;
   // The active quads' tiles, flattened quad-major, are dealt to the grid in
-  // equal contiguous ranges (a range may span two quads: one more T-slice
-  // load).  Round 5 split each quad into G / nact equal slices, which left
+  // contiguous ranges of equal COST (a range may span quads: one more
+  // T-slice load).  Round 5 split each quad into G / nact equal slices, which left
   // G mod nact workgroups idle -- up to a quarter of the grid (52 active
-  // quads: 208 of 256 busy) once quads start to skip.
-  const long long total = (long long)nact * nt;
-  const long long g_end = (long long)(blockIdx.x + 1) * total / G;
-  for (long long pos = (long long)blockIdx.x * total / G; pos < g_end;) {
+  // quads: 208 of 256 busy) once quads start to skip; equal tile counts leave
+  // the workgroups that hold fully rotated quads to finish last once the
+  // others skip blocks.  bound(p): the tile position (quad-major) at cost
+  // offset p, the same function in every workgroup and monotone in p; with
+  // equal costs it is the equal-count deal p / cost.
+  const long long wtotal = (long long)wsum * nt;
+  auto bound = [&](long long p) -> long long {
+    if (p >= wtotal) return (long long)nact * nt;
+    int rq = 0, rt = 0;
+    for (int b0 = 0, seenq = 0, seenw = 0; b0 < nq; b0 += SVDJ_WAVE) {
+      const bool a = active(b0 + lane);
+      const int w = cost(b0 + lane), w1 = w - 1;
+      const unsigned long long ma = __ballot(a), m0 = __ballot(a && (w1 & 1)),
+                               m1 = __ballot(a && (w1 & 2));
+      const int myq = seenq + __popcll(ma & below);
+      const long long lo = (long long)(seenw + __popcll(ma & below) + __popcll(m0 & below) +
+                                       2 * __popcll(m1 & below)) * nt;
+      const unsigned long long hit = __ballot(a && p >= lo && p < lo + (long long)w * nt);
+      if (hit) {
+        const int src_lane = __ffsll((long long)hit) - 1;
+        rq = __shfl(myq, src_lane);
+        rt = __shfl((int)((p - lo) / w), src_lane);
+      }
+      seenq += __popcll(ma);
+      seenw += __popcll(ma) + __popcll(m0) + 2 * __popcll(m1);
+    }
+    return (long long)__builtin_amdgcn_readfirstlane(rq) * nt + __builtin_amdgcn_readfirstlane(rt);
+  };
+  const long long g_end = bound((long long)(blockIdx.x + 1) * wtotal / G);
+  for (long long pos = bound((long long)blockIdx.x * wtotal / G); pos < g_end;) {
     const int qi = (int)(pos / nt);
     const int t0 = (int)(pos % nt);
     const int t1 = (int)((long long)t0 + (g_end - pos) < nt ? (long long)t0 + (g_end - pos) : nt);
@@ -2287,6 +2349,85 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
       }
       cheap = __builtin_amdgcn_readfirstlane(cheap);
     }
+    // SPARSE: what T leaves unchanged is neither computed nor moved.  T is
+    // the identity plus the pairs' plane rotations: a pair that did not
+    // rotate contributes an exact identity block (qbuild_quad_kernel, ns = 0),
+    // so late in a solve most of T - I is exactly zero.  From the values of
+    // the slice (all parts; a sign bit alone is a zero), never from the flags:
+    //   chg  : bit c set when column c of the wave's 32 has a nonzero column in
+    //          T - I: the columns the apply changes.  Others are not stored,
+    //          and with chg == 0 the wave runs no MFMA, epilogue or store.
+    //   nzkb : bit kb set when k block kb (source columns 32 kb .. + 31 of the
+    //          quad, the ones wave kb loads and splits) is nonzero in this
+    //          slice; a zero one is skipped in the MFMA loop.
+    //   src  : the OR of every wave's nzkb (8 words of split image 1 and one
+    //          barrier per item): bit w set when wave w's columns feed some
+    //          wave's product.  A wave with chg == 0 and bit `wave` of src
+    //          clear issues no DMA and no split for the item.
+    // INVARIANT: split skipped by wave w  =>  bit w of src clear  =>  k block w
+    // is zero in every wave's slice  =>  every wave skips it: the stale
+    // fragments (any bit pattern, NaNs included) are never multiplied, not
+    // even by zero.  Every skipped operation contributed an exact zero, so the
+    // results are those of the dense form, but for the sign of a zero: an
+    // untouched -0.0, which x + 0 used to rewrite as +0.0, is now kept.
+    // Every wave reaches every barrier whatever it skips.
+    uint32_t chg = 0, nzkb = 0;
+    {
+      using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+      uint32_t cnz[2] = {0u, 0u};
+#pragma unroll
+      for (int kb = 0; kb < 8; ++kb) {
+        uint32_t ko = 0;
+#pragma unroll
+        for (int cs = 0; cs < 2; ++cs) {
+          uint32_t o = 0;
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            const u32x4 d = __builtin_bit_cast(u32x4, qf[kb][cs][p]);
+            o |= d[0] | d[1] | d[2] | d[3];
+          }
+          cnz[cs] |= o;
+          ko |= o;
+        }
+        if (__ballot((ko & 0x7fff7fffu) != 0)) nzkb |= 1u << kb;
+      }
+#pragma unroll
+      for (int cs = 0; cs < 2; ++cs) {  // lane 16 g + i holds rows of column 16 cs + i
+        const unsigned long long m = __ballot((cnz[cs] & 0x7fff7fffu) != 0);
+        chg |= (uint32_t)((m | m >> 16 | m >> 32 | m >> 48) & 0xffffull) << (16 * cs);
+      }
+      chg = __builtin_amdgcn_readfirstlane(chg);
+      nzkb = __builtin_amdgcn_readfirstlane(nzkb);
+    }
+    // products per tile in quarter units (word 6 counts one unit per cheap
+    // half and two per full half of 4 k blocks)
+    uint32_t qunits = 0;
+    if (chg != 0) {
+#pragma unroll
+      for (int kb = 0; kb < 8; ++kb)
+        if ((nzkb >> kb) & 1u) qunits += NP == 3 && ((cheap >> (kb >> 2)) & 1u) == 0 ? 2u : 1u;
+    }
+    uint32_t src = 0, qsum = 0;
+    {
+      uint32_t* xw = reinterpret_cast<uint32_t*>(lds + L::S_BYTES);
+      if (lane == 0) xw[wave] = nzkb | qunits << 8;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int w = 0; w < 8; ++w) {
+        const uint32_t v = xw[w];
+        src |= v & 0xffu;
+        qsum += v >> 8;
+      }
+      src = __builtin_amdgcn_readfirstlane(src);
+      qsum = __builtin_amdgcn_readfirstlane(qsum);
+    }
+    const bool loads = chg != 0 || ((src >> wave) & 1u) != 0;
+    // store instruction (cs, e) writes columns 16 cs + e + 4 g: issued when one
+    // of them changes, each lane storing its own column only if it does
+    const uint32_t cset = (chg | chg >> 4 | chg >> 8 | chg >> 12) & 0x000f000fu;
+    const int nst = 2 * __popc(cset);  // store instructions per tile, at least
+    const uint32_t lchg = chg >> (4 * g);
     // this wave's 32 columns: block wave >> 1 of [a b c d], half wave & 1
     const int32_t* qp = pairs + 4 * q;
     const int qb = wave >> 1;
@@ -2316,12 +2457,11 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
       constexpr int buf = decltype(bufc)::value;
       constexpr int CH = decltype(chc)::value;  // cheap halves (bit 0: k blocks 0-3, bit 1: 4-7)
       // 1. own DMA of tile t landed (younger: stores of t-1, DMA of t+1)
-      const int younger = (t > t0 ? 16 : 0) + (t + 1 < t1 ? 4 : 0);
+      //    counted from what this wave issues: nst stores, or more (a count
+      //    that is too small only waits longer)
+      const int younger = (t > t0 ? nst : 0) + (t + 1 < t1 ? 4 : 0);
       if constexpr ((ABL & 2) != 0) (void)younger;
-      else if (younger == 20) wait_vmcnt<20>();
-      else if (younger == 16) wait_vmcnt<16>();
-      else if (younger == 4) wait_vmcnt<4>();
-      else wait_vmcnt<0>();
+      else wait_vmcnt_upto(younger);
       const float* R = reinterpret_cast<const float*>(lds + 2 * L::S_BYTES + buf * L::R_BYTES + wave * 4096);
       // 2. split own columns (k block `wave`) into the shared B-fragment image
       //    S[buf]: [kb][rs][part][lane (i, g)] element e = X[16 rs + i][32 kb + 8g + e]
@@ -2360,6 +2500,8 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
           constexpr int k0 = decltype(k0c)::value;
 #pragma unroll
           for (int kb = k0; kb < k0 + 4; ++kb) {
+            // a k block that is zero in this slice (SPARSE: its fragments may be stale)
+            if (((nzkb >> kb) & 1u) == 0) continue;
             bf16x8 xs[NP];
             if constexpr ((ABL & 1) != 0) {
               using i32x4 = __attribute__((ext_vector_type(4))) int;
@@ -2406,24 +2548,44 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
         //    through R[buf] for 16-byte stores cut the compute-only time of the
         //    32x32x16 form 1229 -> 1037 us but not the solve's:
         //    profiles/r6_apply/ablation_vector_epilogue_rejected.jsonl.)
+        //    Only changed columns are stored (SPARSE); all 32 changed is the
+        //    unpredicated form.
+        if (chg == 0xffffffffu) {
 #pragma unroll
-        for (int cs = 0; cs < 2; ++cs) {
-          float v[4];
+          for (int cs = 0; cs < 2; ++cs) {
+            float v[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = R[eb + 512 * cs + 32 * e + 16 * rs];
+            for (int e = 0; e < 4; ++e) v[e] = R[eb + 512 * cs + 32 * e + 16 * rs];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float y = v[e] + (acc[cs][e] + lo[cs][e]);
-            if ((ABL & 2) == 0 || y == -1.2345e-30f)
-              at_u32(own + (size_t)(16 * cs + e) * ld + 16 * rs, st_off) = y;
+            for (int e = 0; e < 4; ++e) {
+              const float y = v[e] + (acc[cs][e] + lo[cs][e]);
+              if ((ABL & 2) == 0 || y == -1.2345e-30f)
+                at_u32(own + (size_t)(16 * cs + e) * ld + 16 * rs, st_off) = y;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int cs = 0; cs < 2; ++cs) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = R[eb + 512 * cs + 32 * e + 16 * rs];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float y = v[e] + (acc[cs][e] + lo[cs][e]);
+              if (((cset >> (16 * cs + e)) & 1u) != 0 && ((lchg >> (16 * cs + e)) & 1u) != 0 &&
+                  ((ABL & 2) == 0 || y == -1.2345e-30f))
+                at_u32(own + (size_t)(16 * cs + e) * ld + 16 * rs, st_off) = y;
+            }
           }
         }
       }
       // 5. tile t + 2 into the raw image this wave just consumed
       if (t + 2 < t1) dma(t + 2, buf);
     };
-    if (t0 < t1) dma(t0, 0);
-    if (t0 + 1 < t1) dma(t0 + 1, 1);
+    if (loads) {
+      if (t0 < t1) dma(t0, 0);
+      if (t0 + 1 < t1) dma(t0 + 1, 1);
+    }
     // the tile loop specialised per cheap-half mask (a branch per k half
     // inside one loop made the compiler spill the T slice)
     auto run = [&](auto chc) {
@@ -2432,19 +2594,44 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
         if (t + 1 < t1) tile(t + 1, std::integral_constant<int, 1>{}, chc);
       }
     };
-    if (cheap == 0) run(std::integral_constant<int, 0>{});
+    if (chg == 0) {
+      // nothing of this wave's changes (SPARSE): it feeds the others -- load
+      // and split as in tile() -- or only keeps the barriers
+      for (int t = t0; t < t1; ++t) {
+        const int buf = (t - t0) & 1;
+        if (loads) {
+          if constexpr ((ABL & 2) == 0) wait_vmcnt_upto(t + 1 < t1 ? 4 : 0);
+          const float* R = reinterpret_cast<const float*>(lds + 2 * L::S_BYTES + buf * L::R_BYTES + wave * 4096);
+          bf16x8* Sw = reinterpret_cast<bf16x8*>(lds + buf * L::S_BYTES) + lane;
+#pragma unroll
+          for (int rs = 0; rs < 2; ++rs) {
+            bf16x8 parts[NP];
+            float xv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xv[e] = R[sb + 32 * e + 16 * rs];
+            split_bf16x8<NP>(xv, parts);
+#pragma unroll
+            for (int i = 0; i < NP; ++i) Sw[((2 * wave + rs) * NP + i) * SVDJ_WAVE] = parts[i];
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (loads && t + 2 < t1) dma(t + 2, buf);
+      }
+    } else if (cheap == 0) run(std::integral_constant<int, 0>{});
     else if constexpr (NP == 3) {
       if (cheap == 1) run(std::integral_constant<int, 1>{});
       else if (cheap == 2) run(std::integral_constant<int, 2>{});
       else run(std::integral_constant<int, 3>{});
     }
-    // work counters of the sweep (metric words 6, 7; svdj_stop.h): MFMAs this
-    // wave issued in 32x32x16 units of 24 (96, 72 or 48 per tile = twice as
-    // many 16x16x32 ones), and tiles moved
-    if (work && lane == 0) {
-      const uint32_t per = NP == 3 ? 4u - (cheap & 1u) - ((cheap >> 1) & 1u) : 2u;
-      atomicAdd(&work[0], (uint32_t)(t1 - t0) * per);
-      if (wave == 0) atomicAdd(&work[1], (uint32_t)(t1 - t0));
+    // work counters of the sweep (metric words 6, 7; svdj_stop.h): MFMAs the
+    // waves issued in 32x32x16 units of 24 (per wave 96, 72 or 48 per tile =
+    // twice as many 16x16x32 ones; a skipped k block or wave adds nothing, the
+    // quarter units of the item's eight waves summed and rounded down once:
+    // less than one unit per item lost), and tiles of active quads walked
+    if (work && lane == 0 && wave == 0) {
+      atomicAdd(&work[0], (uint32_t)(t1 - t0) * qsum >> 2);
+      atomicAdd(&work[1], (uint32_t)(t1 - t0));
     }
     // the next item re-stages both images
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
