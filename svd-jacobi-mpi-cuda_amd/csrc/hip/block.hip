@@ -3088,19 +3088,21 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
   return 0;
 }
 
-// Quad step s (steps s, s+1 fused; see "quad step"): gram, evd 1, T1,
-// update, evd 2, T on the chain's stream.
+// Quad step s (steps s, s+1 fused; see "quad step"): gram (launch_quad_gram),
+// then evd 1, T1, update, evd 2, T (launch_quad_chain) on the chain's stream.
+static bool quad_step_ok(int P, int s, int steps, const int32_t* modes) {
+  if (P % 2 || s + 1 >= steps || !modes || modes[s + 1] != 5) {
+    set_error("quad step %d: needs an even pair count (%d) and a following mode-5 step", s, P);
+    return false;
+  }
+  return true;
+}
+
+// The six cross Grams of quad step s into c.qslabs (c.g.qgch row chunks).
 template <typename T, int W>
-static int launch_quad_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
-                                uint32_t* metric, int mma) {
+static int launch_quad_gram(const Chain<T>& c, int s) {
   if constexpr (sizeof(T) == 4 && W == 64) {
-    if (c.P % 2 || s + 1 >= c.steps || c.modes[s + 1] != 5) {
-      set_error("quad step %d: needs an even pair count (%d) and a following mode-5 step", s, c.P);
-      return -2;
-    }
-    const int b = s & 1;
     const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
-    const int32_t* pr1 = pr + 2 * c.P;
     if (c.gram_np == 2)
       hipLaunchKernelGGL((gram_quad_kernel<0, 2>), dim3(c.P / 2, c.g.qgch), dim3(kGramQThreads), 0,
                          c.st, c.A, c.lda, c.m_pad, pr, c.P, c.g.qgrows, c.qslabs);
@@ -3108,6 +3110,24 @@ static int launch_quad_gram_evd(const Chain<T>& c, int s, double tol, int absmod
       hipLaunchKernelGGL((gram_quad_kernel<0, 3>), dim3(c.P / 2, c.g.qgch), dim3(kGramQThreads), 0,
                          c.st, c.A, c.lda, c.m_pad, pr, c.P, c.g.qgrows, c.qslabs);
     SVDJ_LAUNCH_CHECK();
+    return 0;
+  } else {
+    (void)c; (void)s;
+    set_error("quad steps need fp32 data and W = 64");
+    return -3;
+  }
+}
+
+// Everything of quad step s after its Gram, from the slabs in c.qslabs: evd 1,
+// T1, update, evd 2, T.  (Also what svdj_quad_chain runs, on slabs given by
+// its caller.)
+template <typename T, int W>
+static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
+                             uint32_t* metric, int mma) {
+  if constexpr (sizeof(T) == 4 && W == 64) {
+    const int b = s & 1;
+    const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
+    const int32_t* pr1 = pr + 2 * c.P;
     // many row chunks (few quads): sum them once, wide, for both consumers
     const bool red = c.g.qgch > 4;
     const float* gs = red ? c.qred : c.qslabs;
@@ -3176,6 +3196,14 @@ static int launch_quad_gram_evd(const Chain<T>& c, int s, double tol, int absmod
   }
 }
 
+template <typename T, int W>
+static int launch_quad_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
+                                uint32_t* metric, int mma) {
+  if (sizeof(T) == 4 && W == 64 && !quad_step_ok(c.P, s, c.steps, c.modes)) return -2;
+  const int rc = launch_quad_gram<T, W>(c, s);
+  return rc ? rc : launch_quad_chain<T, W>(c, s, tol, absmode, max_inner, metric, mma);
+}
+
 // Gram + EVD of step s (Q and the skip flags are double-buffered so evd(s+1)
 // never overwrites what apply(s) may still read).
 // Dispatch order of the row chunks (SVDJ_DEBUG stream_order, bit 0: cross
@@ -3188,16 +3216,10 @@ static int stream_order() {
   return v;
 }
 
+// The Gram of step s (mode 0 - 3) into c.slabs (c.g.gchunks row chunks).
 template <typename T, int W>
-static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
-                           uint32_t* metric, int mma) {
-  const int b = s & 1;
+static int launch_gram(const Chain<T>& c, int s, int mode) {
   const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
-  // 0 cross (cyclic EVD), 1 full Gram, 2 cross + bipartite EVD, 3 cross +
-  // cross-only bipartite EVD (evd_cross_kernel)
-  const int mode = c.modes ? c.modes[s] : 0;
-  if (mode == 5) return 0;  // second step of a quad: done by its first (mode 4)
-  if (mode == 4) return launch_quad_gram_evd<T, W>(c, s, tol, absmode, max_inner, metric, mma);
   const int full = mode == 1;
   constexpr int XS = gram_xsplit<T, W>();
   if (full) {
@@ -3216,6 +3238,18 @@ static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, in
                        dim3(kGramThreads), 0, c.st, c.A, c.lda, c.m_pad, pr, c.g.grows, c.slabs);
   }
   SVDJ_LAUNCH_CHECK();
+  return 0;
+}
+
+// Everything of step s (mode 0 - 3) after its Gram, from the slabs in
+// c.slabs: the EVD and, for mode 3, the chunk pre-sum and the Q build.  (Also
+// what svdj_evd_alone runs, on slabs given by its caller.)
+template <typename T, int W>
+static int launch_evd(const Chain<T>& c, int s, int mode, double tol, int absmode, int max_inner,
+                      uint32_t* metric) {
+  const int b = s & 1;
+  const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
+  const int full = mode == 1;
   if (mode == 3) {
     // many row chunks (few pairs per step: the 8-GPU plans read 32): sum them
     // once, wide, instead of on the EVD's critical path (one workgroup per
@@ -3262,6 +3296,18 @@ static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, in
                        max_inner, metric);
   SVDJ_LAUNCH_CHECK();
   return 0;
+}
+
+template <typename T, int W>
+static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
+                           uint32_t* metric, int mma) {
+  // 0 cross (cyclic EVD), 1 full Gram, 2 cross + bipartite EVD, 3 cross +
+  // cross-only bipartite EVD (evd_cross_kernel)
+  const int mode = c.modes ? c.modes[s] : 0;
+  if (mode == 5) return 0;  // second step of a quad: done by its first (mode 4)
+  if (mode == 4) return launch_quad_gram_evd<T, W>(c, s, tol, absmode, max_inner, metric, mma);
+  const int rc = launch_gram<T, W>(c, s, mode);
+  return rc ? rc : launch_evd<T, W>(c, s, mode, tol, absmode, max_inner, metric);
 }
 
 template <typename T, int W>
@@ -3598,6 +3644,138 @@ extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, in
     return -101;
   }
   return 0;
+}
+
+// The middle of a single step alone (tests): launch_evd -- what a step of
+// svdj_block_steps runs after its Gram -- on slabs given by the caller.
+//   slabs   device, data type: P x nchunk x W x W (mode 1: 2W x 2W), the
+//           layout the Gram kernels write; copied into the workspace's slab area
+//   D       squared column norms by block (updated in place), pairs device
+//           int32 [P][2], mode 0 - 3 as launch_gram_evd
+//   Q       out, P x 2W x 2W (data type; a skipped pair's may stay unwritten)
+//   skip    out, int32 [P]
+//   ws      svdj_evd_alone_workspace_bytes: the slab area of a step with
+//           nchunk row chunks, the rotation records and the step counts
+static size_t evd_alone_bytes(int esize, int W, int P, int nchunk) {
+  return rup256((size_t)P * nchunk * 4 * W * W * esize) +
+         rup256((size_t)P * kCrossMaxInner * W * W * esize) + rup256((size_t)P * sizeof(int32_t));
+}
+extern "C" size_t svdj_evd_alone_workspace_bytes(int dtype, int W, int P, int nchunk) {
+  if ((dtype != 0 && dtype != 1) || (W != 32 && W != 64) || P < 1 || nchunk < 1) return 0;
+  return evd_alone_bytes(dtype == 1 ? 8 : 4, W, P, nchunk);
+}
+
+template <typename T, int W>
+static int evd_alone_t(int mode, const void* slabs, int nchunk, void* D, const int32_t* pairs, int P,
+                       double tol, int tol_mode, int max_inner, void* Q, int32_t* skip, void* ws,
+                       uint32_t* metric, hipStream_t st) {
+  Chain<T> c{};
+  c.P = P;
+  c.steps = 1;
+  c.D = (T*)D;
+  c.pairs = pairs;
+  c.st = st;
+  c.g.gchunks = nchunk;
+  char* w = (char*)ws;
+  c.slabs = (T*)w;
+  w += rup256((size_t)P * nchunk * 4 * W * W * sizeof(T));
+  c.rec = (T*)w;
+  w += rup256((size_t)P * kCrossMaxInner * W * W * sizeof(T));
+  c.nsteps = (int32_t*)w;
+  c.Qb[0] = (T*)Q;
+  c.skipb[0] = skip;
+  const size_t in_bytes = (size_t)P * nchunk * (mode == 1 ? 4 : 1) * W * W * sizeof(T);
+  SVDJ_HIP_CHECK(hipMemcpyAsync(c.slabs, slabs, in_bytes, hipMemcpyDeviceToDevice, st));
+  return launch_evd<T, W>(c, 0, mode, tol, tol_mode, max_inner, metric);
+}
+
+extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int nchunk, void* D,
+                              const int32_t* pairs, int P, double tol, int tol_mode, int max_inner,
+                              void* Q, int32_t* skip, void* ws, size_t ws_bytes, uint32_t* metric,
+                              void* stream) {
+  if ((dtype != 0 && dtype != 1) || (W != 32 && W != 64)) {
+    set_error("svdj_evd_alone: unsupported dtype=%d W=%d", dtype, W);
+    return -3;
+  }
+  if (mode < 0 || mode > 3 || P < 1 || nchunk < 1 || max_inner < 0 || (tol_mode != 0 && tol_mode != 1) ||
+      !slabs || !D || !pairs || !Q || !skip || !ws || !metric) {
+    set_error("svdj_evd_alone: bad mode/P/nchunk/max_inner/tol_mode %d/%d/%d/%d/%d or a null pointer",
+              mode, P, nchunk, max_inner, tol_mode);
+    return -2;
+  }
+  const size_t need = evd_alone_bytes(dtype == 1 ? 8 : 4, W, P, nchunk);
+  if (ws_bytes < need) {
+    set_error("svdj_evd_alone: workspace too small: %zu < %zu", ws_bytes, need);
+    return -2;
+  }
+#define SVDJ_EVD_ALONE_ARGS \
+  mode, slabs, nchunk, D, pairs, P, tol, tol_mode, max_inner, Q, skip, ws, metric, (hipStream_t)stream
+  if (dtype == 0 && W == 32) return evd_alone_t<float, 32>(SVDJ_EVD_ALONE_ARGS);
+  if (dtype == 0 && W == 64) return evd_alone_t<float, 64>(SVDJ_EVD_ALONE_ARGS);
+  if (W == 32) return evd_alone_t<double, 32>(SVDJ_EVD_ALONE_ARGS);
+  return evd_alone_t<double, 64>(SVDJ_EVD_ALONE_ARGS);
+#undef SVDJ_EVD_ALONE_ARGS
+}
+
+// The middle of a quad step alone (tests; fp32, W = 64): launch_quad_chain --
+// what a quad step of svdj_block_steps runs after its Gram -- on slabs given
+// by the caller, read in place.
+//   slabs   device fp32, 3P x nchunk x 64 x 64 in svdj_gram_quad's order
+//   pairs   device int32 [2][P][2]: the step's pairs in quad order ((a,c),
+//           (b,d) per quad: mode 4), then those of the next ((a,d), (b,c): mode 5)
+//   np      parts of the split T: 3 / 2 (mma 1 / 2 of svdj_block_steps)
+//   T1      out, fp64 P x 128 x 128; upd out, fp32 P x 64 x 64; Ts out, bf16
+//           (P / 2) x 256 x 256 x np (svdj_apply_quad's layout); skip1, skip2
+//           out, int32 [P] each
+//   ws      svdj_quad_chain_workspace_bytes: the chunk sums, the rotation
+//           records and the step counts
+static size_t quad_chain_bytes(int P) {
+  return rup256((size_t)3 * P * 64 * 64 * sizeof(float)) +
+         rup256((size_t)P * kCrossMaxInner * 64 * 64 * sizeof(float)) +
+         rup256((size_t)P * sizeof(int32_t));
+}
+extern "C" size_t svdj_quad_chain_workspace_bytes(int P) {
+  return P < 2 || P % 2 ? 0 : quad_chain_bytes(P);
+}
+
+extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int32_t* pairs, int P,
+                               double tol, int tol_mode, int max_inner, int np, void* T1, void* upd,
+                               void* Ts, int32_t* skip1, int32_t* skip2, void* ws, size_t ws_bytes,
+                               uint32_t* metric, void* stream) {
+  if (P < 2 || P % 2 || nchunk < 1 || max_inner < 0 || (tol_mode != 0 && tol_mode != 1) ||
+      (np != 2 && np != 3) || !slabs || !D || !pairs || !T1 || !upd || !Ts || !skip1 || !skip2 ||
+      !ws || !metric) {
+    set_error("svdj_quad_chain: bad P/nchunk/max_inner/tol_mode/np %d/%d/%d/%d/%d or a null pointer",
+              P, nchunk, max_inner, tol_mode, np);
+    return -2;
+  }
+  if (ws_bytes < quad_chain_bytes(P)) {
+    set_error("svdj_quad_chain: workspace too small: %zu < %zu", ws_bytes, quad_chain_bytes(P));
+    return -2;
+  }
+  static const int32_t modes[2] = {4, 5};
+  Chain<float> c{};
+  c.P = P;
+  c.steps = 2;
+  c.D = (float*)D;
+  c.pairs = pairs;
+  c.modes = modes;
+  c.st = (hipStream_t)stream;
+  c.g.qgch = nchunk;
+  c.qslabs = const_cast<float*>((const float*)slabs);  // only read after the Gram
+  char* w = (char*)ws;
+  c.qred = (float*)w;
+  w += rup256((size_t)3 * P * 64 * 64 * sizeof(float));
+  c.rec = (float*)w;
+  w += rup256((size_t)P * kCrossMaxInner * 64 * 64 * sizeof(float));
+  c.nsteps = (int32_t*)w;
+  c.T1 = (double*)T1;
+  c.upd = (float*)upd;
+  c.Ts[0] = (bf16x8*)Ts;
+  c.skip1[0] = skip1;
+  c.skip2[0] = skip2;
+  if (!quad_step_ok(c.P, 0, c.steps, c.modes)) return -2;
+  return launch_quad_chain<float, 64>(c, 0, tol, tol_mode, max_inner, metric, np == 2 ? 2 : 1);
 }
 
 // Test/diagnostic hook: X <- X Q for ONE column-block pair (blocks 0 and 1 of

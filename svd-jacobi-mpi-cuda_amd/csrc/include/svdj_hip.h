@@ -144,6 +144,41 @@ int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld, const voi
 int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, int ldv, const int32_t* pairs,
                     int nq, const void* Ts, const int32_t* skip1, const int32_t* skip2, int np,
                     int grid, int cheap_log2, uint32_t* work, void* stream);
+// The middle of a single step alone: everything a step of svdj_block_steps
+// runs after its Gram (mode 0 cyclic EVD, 1 full Gram + cyclic EVD, 2
+// bipartite EVD, 3 cross EVD + chunk pre-sum + Q build, selected by P and
+// nchunk as in a solve), from Gram slabs given by the caller.
+//   slabs   device, data type: P x nchunk x W x W (mode 1: 2W x 2W), summed
+//           over the nchunk chunks by the kernels
+//   D       device, squared column norms by block id; updated in place
+//   pairs   device int32 [P][2]; metric: device uint32[8] (svdj_stop.h),
+//           floor set
+//   Q       out, P x 2W x 2W row-major (a skipped pair's is not written)
+//   skip    out, int32 [P]
+//   ws      device, svdj_evd_alone_workspace_bytes(dtype, W, P, nchunk) bytes
+// Returns -2 with the error string set, nothing launched, on a bad argument.
+size_t svdj_evd_alone_workspace_bytes(int dtype, int W, int P, int nchunk);
+int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int nchunk, void* D,
+                   const int32_t* pairs, int P, double tol, int tol_mode, int max_inner, void* Q,
+                   int32_t* skip, void* ws, size_t ws_bytes, uint32_t* metric, void* stream);
+// The middle of a quad step alone (fp32, W = 64): everything a quad step runs
+// between its Gram and its apply (chunk pre-sum, EVD 1, T1, Gram-space update,
+// EVD 2, split T; variants selected by P and nchunk as in a solve).
+//   slabs   device fp32, 3P x nchunk x 64 x 64 in svdj_gram_quad's order
+//   pairs   device int32 [2][P][2]: quad order (a,c), (b,d), then (a,d), (b,c)
+//   np      2 or 3 parts of the split T
+//   T1      out, fp64 P x 128 x 128 (identity for a pair EVD 1 skipped)
+//   upd     out, fp32 P x 64 x 64: the couplings EVD 2 reads
+//   Ts      out, bf16 (P / 2) x 256 x 256 x np in svdj_apply_quad's layout
+//   skip1, skip2  out, int32 [P] each
+//   ws      device, svdj_quad_chain_workspace_bytes(P) bytes
+// Returns -2 with the error string set, nothing launched, on a bad argument
+// (odd P included).
+size_t svdj_quad_chain_workspace_bytes(int P);
+int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int32_t* pairs, int P, double tol,
+                    int tol_mode, int max_inner, int np, void* T1, void* upd, void* Ts,
+                    int32_t* skip1, int32_t* skip2, void* ws, size_t ws_bytes, uint32_t* metric,
+                    void* stream);
 
 // ---------------------------------------------------------------------------
 // Post-processing / utilities.

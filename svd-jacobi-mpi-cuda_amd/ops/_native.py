@@ -131,6 +131,14 @@ def hip_lib():
         _sig(lib, "svdj_apply_quad", c_int,
              [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
               c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])
+        _sig(lib, "svdj_evd_alone_workspace_bytes", c_size_t, [c_int, c_int, c_int, c_int])
+        _sig(lib, "svdj_evd_alone", c_int,
+             [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_int,
+              c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p])
+        _sig(lib, "svdj_quad_chain_workspace_bytes", c_size_t, [c_int])
+        _sig(lib, "svdj_quad_chain", c_int,
+             [c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int, c_void_p,
+              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p])
         _sig(lib, "svdj_set_identity", c_int,
              [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
         _sig(lib, "svdj_col_norms2", c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])

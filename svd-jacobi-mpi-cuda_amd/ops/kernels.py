@@ -457,6 +457,92 @@ def apply_quad(At, Vt, m_pad, pairs, Ts, skip1, skip2, np: int = 3, grid: int = 
                                         _stream(At)), "apply_quad")
 
 
+def _check_chain_args(what, slabs, D, pairs, metric, nb_of_d):
+    dev = slabs.device
+    if not slabs.is_cuda or not slabs.is_contiguous():
+        raise ValueError(f"{what}: slabs must be a contiguous device tensor")
+    if D.dtype != slabs.dtype or D.device != dev or D.dim() != 1 or not D.is_contiguous():
+        raise ValueError(f"{what}: D must be a contiguous 1-D tensor of the slabs' type and device")
+    hp = pairs.cpu()
+    if int(hp.min()) < 0 or int(hp.max()) >= nb_of_d:
+        raise ValueError(f"{what}: block index outside [0, {nb_of_d})")
+    if (metric.dtype != torch.int32 or metric.device != dev or not metric.is_contiguous()
+            or metric.numel() < METRIC_WORDS):
+        raise ValueError(f"{what}: metric must be new_metric(device)")
+
+
+def evd_alone(slabs, D, pairs, W: int, mode: int, tol: float, max_inner: int, metric,
+              tol_mode="relative", Q: torch.Tensor | None = None):
+    """The middle of a single block step alone (csrc/hip/block.hip launch_evd,
+    what a step runs after its Gram): ``slabs`` (P, nchunk, W, W), or (P,
+    nchunk, 2W, 2W) for ``mode`` 1, device fp32 / fp64 in the layout the Gram
+    kernels write; ``D`` squared column norms by block id (updated in place);
+    ``pairs`` (P, 2) block ids; ``mode`` 0 cyclic, 1 full, 2 bipartite, 3
+    cross (+ chunk pre-sum and Q build, selected by P and nchunk as in a
+    solve).  Returns (Q (P, 2W, 2W), skip (P,) int32); the Q of a skipped pair
+    is not written (``Q``: the buffer to write into, e.g. pre-filled)."""
+    check_block(slabs.dtype, W)
+    P, nchunk = int(slabs.shape[0]), int(slabs.shape[1])
+    side = 2 * W if mode == 1 else W
+    if mode not in (0, 1, 2, 3) or slabs.dim() != 4 or tuple(slabs.shape[2:]) != (side, side):
+        raise ValueError(f"evd_alone: mode 0-3 and slabs (P, nchunk, {side}, {side})")
+    if pairs.dim() != 2 or tuple(pairs.shape) != (P, 2):
+        raise ValueError("evd_alone: pairs must be (P, 2)")
+    _check_chain_args("evd_alone", slabs, D, pairs, metric, D.numel() // W)
+    dev = slabs.device
+    pairs = pairs.to(torch.int32).contiguous().to(dev)
+    if Q is None:
+        Q = torch.zeros(P, 2 * W, 2 * W, dtype=slabs.dtype, device=dev)
+    elif (Q.dtype != slabs.dtype or Q.device != dev or not Q.is_contiguous()
+          or tuple(Q.shape) != (P, 2 * W, 2 * W)):
+        raise ValueError("evd_alone: Q must be contiguous (P, 2W, 2W) of the slabs' type and device")
+    skip = torch.zeros(P, dtype=torch.int32, device=dev)
+    lib = hip_lib()
+    nbytes = int(lib.svdj_evd_alone_workspace_bytes(dtype_code(slabs.dtype), W, P, nchunk))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    hip_check(lib.svdj_evd_alone(dtype_code(slabs.dtype), W, int(mode), _ptr(slabs), nchunk, _ptr(D),
+                                 _ptr(pairs), P, float(tol), tol_mode_code(tol_mode), int(max_inner),
+                                 _ptr(Q), _ptr(skip), _ptr(ws), ws.numel(), _ptr(metric),
+                                 _stream(slabs)), "evd_alone")
+    return Q, skip
+
+
+def quad_chain(slabs, D, pairs0, pairs1, tol: float, max_inner: int, metric, np: int = 3,
+               tol_mode="relative"):
+    """The middle of a quad step alone (fp32, W = 64; csrc/hip/block.hip
+    launch_quad_chain, what a quad step runs between its Gram and its apply):
+    ``slabs`` (3P, nchunk, 64, 64) in :func:`gram_quad`'s order, ``D`` squared
+    column norms by block id (updated in place), ``pairs0`` (P, 2) in quad
+    order ((a, c), (b, d)) and ``pairs1`` ((a, d), (b, c)).  Returns a dict:
+    ``T1`` (P, 128, 128) fp64, ``upd`` (P, 64, 64), ``Ts`` (bfloat16, (P / 2)
+    * 256 * 256 * np, :func:`apply_quad`'s layout), ``skip1``, ``skip2``."""
+    if slabs.dtype != torch.float32 or slabs.dim() != 4 or tuple(slabs.shape[2:]) != (64, 64) \
+            or slabs.shape[0] % 6 or slabs.shape[0] == 0:
+        raise ValueError("quad_chain: fp32 slabs (3P, nchunk, 64, 64), P even")
+    P, nchunk = int(slabs.shape[0]) // 3, int(slabs.shape[1])
+    if tuple(pairs0.shape) != (P, 2) or tuple(pairs1.shape) != (P, 2):
+        raise ValueError("quad_chain: pairs0, pairs1 must be (P, 2)")
+    pairs = torch.stack([pairs0.cpu(), pairs1.cpu()]).to(torch.int32).contiguous()
+    _check_chain_args("quad_chain", slabs, D, pairs, metric, D.numel() // 64)
+    if np not in (2, 3):
+        raise ValueError("quad_chain: np 2 or 3")
+    dev = slabs.device
+    pairs = pairs.to(dev)
+    out = {"T1": torch.zeros(P, 128, 128, dtype=torch.float64, device=dev),
+           "upd": torch.zeros(P, 64, 64, dtype=torch.float32, device=dev),
+           "Ts": torch.zeros(P // 2 * 256 * 256 * int(np), dtype=torch.bfloat16, device=dev),
+           "skip1": torch.zeros(P, dtype=torch.int32, device=dev),
+           "skip2": torch.zeros(P, dtype=torch.int32, device=dev)}
+    lib = hip_lib()
+    ws = torch.empty(int(lib.svdj_quad_chain_workspace_bytes(P)), dtype=torch.uint8, device=dev)
+    hip_check(lib.svdj_quad_chain(_ptr(slabs), nchunk, _ptr(D), _ptr(pairs), P, float(tol),
+                                  tol_mode_code(tol_mode), int(max_inner), int(np), _ptr(out["T1"]),
+                                  _ptr(out["upd"]), _ptr(out["Ts"]), _ptr(out["skip1"]),
+                                  _ptr(out["skip2"]), _ptr(ws), ws.numel(), _ptr(metric),
+                                  _stream(slabs)), "quad_chain")
+    return out
+
+
 def block_solve(At, Vt, D, m_pad, W, tol, max_inner, max_sweeps, mma="native",
                 tol_mode="relative", inner_order="cyclic", stop_rule="second_order"):
     """Single-device block Jacobi (round-robin over ncols/W blocks, first
@@ -505,5 +591,5 @@ __all__ = [
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
     "block_workspace", "block_steps", "block_solve", "check_block", "MMA_CODES", "mma_code",
     "apply_q", "apply_quad",
-    "gram_cross", "gram_quad",
+    "gram_cross", "gram_quad", "evd_alone", "quad_chain",
 ]

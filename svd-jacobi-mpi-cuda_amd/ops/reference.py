@@ -74,6 +74,21 @@ def round_robin_pairs(N):
     return out
 
 
+def ring_pairs(N):
+    """The cyclic ordering as evd_kernel steps through it (block.hip
+    ring_slot): at step st slot a pairs player N-1 (a = 0) or the player at
+    ring position a-1 with the one at position N-2-a; the player at position x
+    after st steps is ((x - st) mod (N-1) + 1) mod (N-1).  The same pairs per
+    sweep as round_robin_pairs, in another order of steps."""
+    R = N - 1
+
+    def player(pos, st):
+        return ((pos - st) % R + 1) % R
+
+    return [[(N - 1 if a == 0 else player(a - 1, st), player(N - 2 - a, st)) for a in range(N // 2)]
+            for st in range(R)]
+
+
 _RR_CACHE = {}
 
 
@@ -85,7 +100,7 @@ def bipartite_pairs(W):
 
 
 def jacobi_evd(G, tol, max_sweeps, tol_mode: int = 0, order: str = "cyclic", floor: float = 0.0,
-               stats: dict | None = None):
+               stats: dict | None = None, lookahead: bool = False):
     """Cyclic parallel Jacobi EVD of a batch of SPD matrices G (P, N, N).
 
     Same orderings (``cyclic``: circle-method round robin over all pairs;
@@ -96,15 +111,20 @@ def jacobi_evd(G, tol, max_sweeps, tol_mode: int = 0, order: str = "cyclic", flo
     with ``stats`` (a dict) the second-order stop test's inputs
     (csrc/include/svdj_stop.h) accumulate: ``smax`` the largest effective
     sine (|s| times the larger norm ratio after the rotation) and ``ncols``
-    the number of column rotations applied.
+    the number of column rotations applied.  ``order`` ``ring``: cyclic in
+    evd_kernel's own order of steps (ring_pairs).  ``lookahead``: the
+    statistics also take in, for every matrix whose last sweep rotated, the
+    rotations of step 0 of the sweep after it, solved but not applied --
+    evd_kernel solves every step one step ahead and counts what it solved.
     """
     G = G.clone()
     P, N, _ = G.shape
     Q = torch.eye(N, dtype=G.dtype).expand(P, N, N).clone()
-    key = (N, "cyclic" if order == "cyclic" else "bipartite")
+    key = (N, order if order in ("cyclic", "ring") else "bipartite")
     sched = _RR_CACHE.get(key)
     if sched is None:
-        prs_all = round_robin_pairs(N) if order == "cyclic" else bipartite_pairs(N // 2)
+        prs_all = (round_robin_pairs(N) if order == "cyclic" else ring_pairs(N) if order == "ring"
+                   else bipartite_pairs(N // 2))
         sched = [(torch.tensor([a for a, b in prs]), torch.tensor([b for a, b in prs]))
                  for prs in prs_all]
         _RR_CACHE[key] = sched
@@ -117,13 +137,18 @@ def jacobi_evd(G, tol, max_sweeps, tol_mode: int = 0, order: str = "cyclic", flo
         within.fill_diagonal_(False)
         G[:, within] = 0
     rotated = torch.zeros(P, dtype=torch.bool)
-    for _ in range(max_sweeps):
+    sweep_rot = torch.zeros(P, dtype=torch.bool)
+    for sw in range(max_sweeps + (1 if lookahead and stats is not None else 0)):
+        ahead = sw == max_sweeps  # the look-ahead step: statistics only
+        live = sweep_rot
         sweep_rot = torch.zeros(P, dtype=torch.bool)
-        for p, q in sched:
+        for p, q in (sched[:1] if ahead else sched):
             gpp, gqq, gpq = G[:, p, p], G[:, q, q], G[:, p, q]
             nrm = gpp.clamp(min=0).sqrt() * gqq.clamp(min=0).sqrt()
             rot = (gpq.abs() > tol) if tol_mode == 1 else (
                 (nrm > 0) & (gpq.abs() > tol * nrm) & (torch.minimum(gpp, gqq) > floor))
+            if ahead:
+                rot = rot & live[:, None]
             if not bool(rot.any()):
                 continue
             sweep_rot |= rot.any(1)
@@ -139,6 +164,12 @@ def jacobi_evd(G, tol, max_sweeps, tol_mode: int = 0, order: str = "cyclic", flo
                 eff = torch.where(rot, eff, torch.zeros_like(eff))
                 stats["smax"] = max(stats.get("smax", 0.0), float(eff.max()))
                 stats["ncols"] = stats.get("ncols", 0) + int(rot.sum())
+                # the same per matrix of the batch
+                stats["smax_each"] = torch.maximum(stats.get("smax_each", torch.zeros(P, dtype=eff.dtype)),
+                                                   eff.max(1).values)
+                stats["ncols_each"] = stats.get("ncols_each", torch.zeros(P, dtype=torch.long)) + rot.sum(1)
+            if ahead:
+                break
             Gp, Gq = G[:, p, :].clone(), G[:, q, :].clone()
             G[:, p, :] = c[:, :, None] * Gp - s[:, :, None] * Gq
             G[:, q, :] = s[:, :, None] * Gp + c[:, :, None] * Gq
