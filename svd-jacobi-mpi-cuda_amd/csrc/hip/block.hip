@@ -2953,44 +2953,11 @@ static Geometry make_geometry(int W, int P, int m_pad, int n_v, int mma = 0) {
   return g;
 }
 
-static size_t rup256(size_t b) { return (b + 255) / 256 * 256; }
-// Quad-step scratch (fp32 W = 64, only when the step list has quad steps):
-// the 3P Gram slabs, T1 (fp64 Q of the P step-s pairs), the step-(s+1)
-// couplings, the double-buffered split T - I (P/2 quads x 256 x 256 in 3
-// bf16 parts = 1.5 x an fp32 T each) and the skip flags of both EVDs
-// (chain_init's layout).
 static bool has_quad(int esize, int W) { return esize == 4 && W == 64; }
-static size_t quad_bytes(int P, int m_pad) {
-  Geometry g;
-  quad_geometry(g, P, m_pad, 0);
-  constexpr int W = 64;
-  const size_t kstride = rup256((size_t)P * sizeof(int32_t));
-  const size_t tstride = rup256((size_t)(P / 2 > 0 ? P / 2 : 1) * 16 * W * W * sizeof(float));
-  return rup256((size_t)3 * P * g.qgch * W * W * sizeof(float)) +
-         rup256((size_t)3 * P * W * W * sizeof(float)) +
-         rup256((size_t)P * 4 * W * W * sizeof(double)) + rup256((size_t)P * W * W * sizeof(float)) +
-         3 * tstride + 4 * kstride;
-}
 static bool has_quad_steps(const int32_t* modes, int steps) {
   for (int s = 0; modes && s < steps; ++s)
     if (modes[s] == 4) return true;
   return false;
-}
-static size_t ws_bytes_for(int esize, int W, int P, int m_pad, bool quad) {
-  // the Gram chunking depends on the apply mode (split-bf16 launches may take
-  // more chunks): size the slabs for the larger of the two
-  Geometry g = make_geometry(W, P, m_pad, 0, 0);
-  const Geometry gs = make_geometry(W, P, m_pad, 0, 1);
-  if (gs.gchunks > g.gchunks) g = gs;
-  size_t slabs = (size_t)P * g.gchunks * 4 * W * W * esize;
-  size_t q = (size_t)P * 4 * W * W * esize;
-  size_t sk = (size_t)P * sizeof(int32_t);
-  size_t rec = (size_t)P * kCrossMaxInner * W * W * esize;
-  // slabs + double-buffered Q and skip flags (evd(s+1) may run while apply(s)
-  // reads) + the cross EVD's rotation records and step counts (consumed by
-  // qbuild(s) before evd(s+1) on the same stream: single-buffered)
-  return rup256(slabs) + 2 * rup256(q) + 2 * rup256(sk) + rup256(rec) + rup256(sk) +
-         (quad && has_quad(esize, W) ? quad_bytes(P, m_pad) : 0);
 }
 
 // One chain of steps: resident buffers, its pair list and its workspace.
@@ -3002,6 +2969,7 @@ struct Chain {
   const int32_t* modes;
   Geometry g;
   T* slabs;
+  T* xsum;  // cross slabs summed over their row chunks, inside the slab area (launch_evd)
   T* Qb[2];
   int32_t* skipb[2];
   T* rec;  // cross EVD rotation records (tangents)
@@ -3019,6 +2987,101 @@ struct Chain {
   int shared;  // another chain runs concurrently on this GPU (svdj_block_steps mma bit 9)
 };
 
+// Workspace areas in the order they are taken, each rounded up to 256 bytes.
+// With a null base nothing is handed out and `off` ends as the byte count,
+// so one layout routine gives a workspace's size and its carve-up.
+static size_t rup256(size_t b) { return (b + 255) / 256 * 256; }
+struct Bump {
+  char* base;
+  size_t off;
+  template <typename T>
+  T* take(size_t bytes) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += rup256(bytes);
+    return p;
+  }
+};
+
+// The layout routines below read c.P and the chunk counts in c.g, set the
+// chain's workspace pointers (null for a null ws) and return the byte count.
+
+// c.g.gchunks full-Gram (2W x 2W) slabs per pair; cross slabs (W x W) fill
+// the first quarter, and their sums over the chunks (launch_evd) follow them.
+template <typename T>
+static void take_slabs(Chain<T>& c, Bump& b, int W) {
+  c.slabs = b.take<T>((size_t)c.P * c.g.gchunks * 4 * W * W * sizeof(T));
+  c.xsum = c.slabs ? c.slabs + (size_t)c.P * c.g.gchunks * W * W : nullptr;
+}
+// The cross EVD's rotation records and step counts (consumed by qbuild(s)
+// before evd(s+1) on the same stream: single-buffered).
+template <typename T>
+static void take_records(Chain<T>& c, Bump& b, int W) {
+  c.rec = b.take<T>((size_t)c.P * kCrossMaxInner * W * W * sizeof(T));
+  c.nsteps = b.take<int32_t>((size_t)c.P * sizeof(int32_t));
+}
+
+// A solve's workspace: slabs, double-buffered Q and skip flags (evd(s+1) may
+// run while apply(s) reads), records.  With quad steps (fp32 W = 64) also the
+// 3P quad Gram slabs and their chunk sums, T1 (fp64 Q of the P step-s pairs),
+// the step-(s+1) couplings, the double-buffered split T - I (P/2 quads x 256
+// x 256 in 3 bf16 parts = 1.5 x an fp32 T each) and both EVDs' skip flags.
+template <typename T>
+static size_t solve_layout(Chain<T>& c, void* ws, int W, bool quad) {
+  Bump b{(char*)ws, 0};
+  const size_t P = c.P, flags = P * sizeof(int32_t);
+  take_slabs(c, b, W);
+  for (T*& q : c.Qb) q = b.take<T>(P * 4 * W * W * sizeof(T));
+  for (int32_t*& k : c.skipb) k = b.take<int32_t>(flags);
+  take_records(c, b, W);
+  if (quad && has_quad(sizeof(T), W)) {
+    c.qslabs = b.take<float>(3 * P * c.g.qgch * W * W * sizeof(float));
+    c.qred = b.take<float>(3 * P * W * W * sizeof(float));
+    c.T1 = b.take<double>(P * 4 * W * W * sizeof(double));
+    c.upd = b.take<float>(P * W * W * sizeof(float));
+    const size_t tstride = rup256((size_t)(c.P / 2 > 0 ? c.P / 2 : 1) * 16 * W * W * sizeof(float));
+    c.Ts[0] = b.take<bf16x8>(3 * tstride);  // 3 bf16 parts = 1.5 x the fp32 size of T
+    c.Ts[1] = c.Ts[0] ? (bf16x8*)((char*)c.Ts[0] + 3 * tstride / 2) : nullptr;
+    for (int32_t*& k : c.skip1) k = b.take<int32_t>(flags);
+    for (int32_t*& k : c.skip2) k = b.take<int32_t>(flags);
+  }
+  return b.off;
+}
+// svdj_evd_alone's: the slab area of a step with c.g.gchunks chunks, records.
+template <typename T>
+static size_t evd_alone_layout(Chain<T>& c, void* ws, int W) {
+  Bump b{(char*)ws, 0};
+  take_slabs(c, b, W);
+  take_records(c, b, W);
+  return b.off;
+}
+template <typename T>
+static size_t evd_alone_ws_bytes(int W, int P, int nchunk) {
+  Chain<T> c{};
+  c.P = P;
+  c.g.gchunks = nchunk;
+  return evd_alone_layout(c, nullptr, W);
+}
+// svdj_quad_chain's: the chunk sums of the 3P quad Grams, records.
+static size_t quad_chain_layout(Chain<float>& c, void* ws) {
+  Bump b{(char*)ws, 0};
+  c.qred = b.take<float>((size_t)3 * c.P * 64 * 64 * sizeof(float));
+  take_records(c, b, 64);
+  return b.off;
+}
+
+// Bytes of a solve's workspace.  The Gram chunking depends on the apply mode
+// (split-bf16 launches may take more chunks): the slabs are sized for the
+// larger of the two, whichever chain_init then carves.
+template <typename T>
+static size_t solve_ws_bytes(int W, int P, int m_pad, bool quad) {
+  Chain<T> c{};
+  c.P = P;
+  c.g = make_geometry(W, P, m_pad, 0, 0);
+  const Geometry gs = make_geometry(W, P, m_pad, 0, 1);
+  if (gs.gchunks > c.g.gchunks) c.g = gs;
+  return solve_layout(c, nullptr, W, quad);
+}
+
 template <typename T, int W>
 static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int ldv, T* D,
                       const int32_t* pairs, int P, int steps, const int32_t* modes, void* ws,
@@ -3028,7 +3091,7 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
     set_error("quad steps need fp32 data and W = 64");
     return -3;
   }
-  const size_t need = ws_bytes_for(sizeof(T), W, P, m_pad, quad);
+  const size_t need = solve_ws_bytes<T>(W, P, m_pad, quad);
   if (ws_bytes < need) {
     set_error("workspace too small: %zu < %zu", ws_bytes, need);
     return -4;
@@ -3041,50 +3104,12 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
     set_error("fp32 W = 64 needs lda %% 4 == 0, got %d", lda);
     return -2;
   }
+  c = Chain<T>{};
   c.m_pad = m_pad; c.lda = lda; c.n_v = n_v; c.ldv = ldv; c.P = P; c.steps = steps;
   c.gram_np = 3;
-  c.shared = 0;
   c.A = A; c.V = V; c.D = D; c.pairs = pairs; c.modes = modes; c.st = st;
   c.g = make_geometry(W, P, m_pad, V ? n_v : 0, mma);
-  char* w = (char*)ws;
-  c.slabs = (T*)w;
-  w += ((size_t)P * c.g.gchunks * 4 * W * W * sizeof(T) + 255) / 256 * 256;
-  const size_t qstride = ((size_t)P * 4 * W * W * sizeof(T) + 255) / 256 * 256;
-  c.Qb[0] = (T*)w;
-  c.Qb[1] = (T*)(w + qstride);
-  w += 2 * qstride;
-  const size_t kstride = ((size_t)P * sizeof(int32_t) + 255) / 256 * 256;
-  c.skipb[0] = (int32_t*)w;
-  c.skipb[1] = (int32_t*)(w + kstride);
-  w += 2 * kstride;
-  c.rec = (T*)w;
-  w += rup256((size_t)P * kCrossMaxInner * W * W * sizeof(T));
-  c.nsteps = (int32_t*)w;
-  w += kstride;
-  c.qslabs = nullptr;
-  c.qred = nullptr;
-  c.T1 = nullptr;
-  c.upd = nullptr;
-  c.Ts[0] = c.Ts[1] = nullptr;
-  c.skip1[0] = c.skip1[1] = c.skip2[0] = c.skip2[1] = nullptr;
-  if (quad) {
-    c.qslabs = (float*)w;
-    w += rup256((size_t)3 * P * c.g.qgch * W * W * sizeof(float));
-    c.qred = (float*)w;
-    w += rup256((size_t)3 * P * W * W * sizeof(float));
-    c.T1 = (double*)w;
-    w += rup256((size_t)P * 4 * W * W * sizeof(double));
-    c.upd = (float*)w;
-    w += rup256((size_t)P * W * W * sizeof(float));
-    const size_t tstride = rup256((size_t)(P / 2 > 0 ? P / 2 : 1) * 16 * W * W * sizeof(float));
-    c.Ts[0] = (bf16x8*)w;  // 3 bf16 parts = 1.5 x the fp32 size of T
-    c.Ts[1] = (bf16x8*)(w + 3 * tstride / 2);
-    w += 3 * tstride;
-    c.skip1[0] = (int32_t*)w;
-    c.skip1[1] = (int32_t*)(w + kstride);
-    c.skip2[0] = (int32_t*)(w + 2 * kstride);
-    c.skip2[1] = (int32_t*)(w + 3 * kstride);
-  }
+  solve_layout(c, ws, W, quad);
   return 0;
 }
 
@@ -3098,17 +3123,24 @@ static bool quad_step_ok(int P, int s, int steps, const int32_t* modes) {
   return true;
 }
 
+// f(np) with the number of bf16 parts, 2 or (any other value) 3, as a
+// compile-time constant: decltype(np)::value.
+template <typename F>
+static void with_parts(int np, F&& f) {
+  if (np == 2) return f(std::integral_constant<int, 2>{});
+  f(std::integral_constant<int, 3>{});
+}
+
 // The six cross Grams of quad step s into c.qslabs (c.g.qgch row chunks).
 template <typename T, int W>
 static int launch_quad_gram(const Chain<T>& c, int s) {
   if constexpr (sizeof(T) == 4 && W == 64) {
     const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
-    if (c.gram_np == 2)
-      hipLaunchKernelGGL((gram_quad_kernel<0, 2>), dim3(c.P / 2, c.g.qgch), dim3(kGramQThreads), 0,
-                         c.st, c.A, c.lda, c.m_pad, pr, c.P, c.g.qgrows, c.qslabs);
-    else
-      hipLaunchKernelGGL((gram_quad_kernel<0, 3>), dim3(c.P / 2, c.g.qgch), dim3(kGramQThreads), 0,
-                         c.st, c.A, c.lda, c.m_pad, pr, c.P, c.g.qgrows, c.qslabs);
+    with_parts(c.gram_np, [&](auto np) {
+      hipLaunchKernelGGL((gram_quad_kernel<0, decltype(np)::value>), dim3(c.P / 2, c.g.qgch),
+                         dim3(kGramQThreads), 0, c.st, c.A, c.lda, c.m_pad, pr, c.P, c.g.qgrows,
+                         c.qslabs);
+    });
     SVDJ_LAUNCH_CHECK();
     return 0;
   } else {
@@ -3175,18 +3207,15 @@ static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, 
                        max_inner, metric);
     SVDJ_LAUNCH_CHECK();
     // the split T is written directly (no tsplit pass)
-    if (lat && mma == 2)
-      hipLaunchKernelGGL((qbuild_quad_kernel<2, 2, QBT, 2>), dim3(c.P, 256 / (2 * QBW)), dim3(QBT), 0,
-                         c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
-    else if (lat)
-      hipLaunchKernelGGL((qbuild_quad_kernel<2, 2, QBT, 3>), dim3(c.P, 256 / (2 * QBW)), dim3(QBT), 0,
-                         c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
-    else if (mma == 2)
-      hipLaunchKernelGGL((qbuild_quad_kernel<2, R, QBT, 2>), dim3(c.P, 256 / (R * QBW)), dim3(QBT),
-                         0, c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
-    else
-      hipLaunchKernelGGL((qbuild_quad_kernel<2, R, QBT, 3>), dim3(c.P, 256 / (R * QBW)), dim3(QBT),
-                         0, c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
+    with_parts(mma == 2 ? 2 : 3, [&](auto np) {
+      constexpr int NP = decltype(np)::value;
+      if (lat)
+        hipLaunchKernelGGL((qbuild_quad_kernel<2, 2, QBT, NP>), dim3(c.P, 256 / (2 * QBW)),
+                           dim3(QBT), 0, c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
+      else
+        hipLaunchKernelGGL((qbuild_quad_kernel<2, R, QBT, NP>), dim3(c.P, 256 / (R * QBW)),
+                           dim3(QBT), 0, c.st, c.rec, c.nsteps, c.skip2[b], c.T1, c.Ts[b]);
+    });
     SVDJ_LAUNCH_CHECK();
     return 0;
   } else {
@@ -3259,11 +3288,10 @@ static int launch_evd(const Chain<T>& c, int s, int mode, double tol, int absmod
     if constexpr (sizeof(T) == 4 && W == 64) {
       static const int red_from = svdj_debug_knob("cross_reduce_chunks", 9);  // A/B only
       if (gn >= red_from) {
-        float* red = c.slabs + (size_t)c.P * gn * W * W;  // inside the full-Gram slab area
         hipLaunchKernelGGL(slab_reduce_kernel, dim3(c.P, W * W / 4 / kRedThreads), dim3(kRedThreads),
-                           0, c.st, c.slabs, gn, red);
+                           0, c.st, c.slabs, gn, c.xsum);
         SVDJ_LAUNCH_CHECK();
-        gs = red;
+        gs = c.xsum;
         gn = 1;
       }
     }
@@ -3310,6 +3338,27 @@ static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, in
   return rc ? rc : launch_evd<T, W>(c, s, mode, tol, absmode, max_inner, metric);
 }
 
+// The apply of quad step s (T-stationary, persistent: apply_quad_ts_kernel<np>
+// on `grid` workgroups) on A and V with T - I from c.Ts, for the c.P / 2 quads
+// of the step's pairs.  cheap_tol: the bound on |T - I| of a cheap k half
+// (np == 2 takes the kernel's default); work: its work counters, or null.
+// (Also what svdj_apply_quad runs, on a T given by its caller.)
+static int launch_quad_apply(const Chain<float>& c, int s, int np, int grid, float cheap_tol,
+                             uint32_t* work) {
+  const int b = s & 1;
+  const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
+  const int nq = c.P / 2, at = c.m_pad / 32, vt = c.V ? c.n_v / 32 : 0;
+  if (np == 3)
+    hipLaunchKernelGGL((apply_quad_ts_kernel<3>), dim3(grid), dim3(kQuadTsThreads), 0, c.st, c.A,
+                       c.lda, at, c.V, c.ldv, vt, pr, nq, c.Ts[b], c.skip1[b], c.skip2[b], work,
+                       cheap_tol);
+  else
+    hipLaunchKernelGGL((apply_quad_ts_kernel<2>), dim3(grid), dim3(kQuadTsThreads), 0, c.st, c.A,
+                       c.lda, at, c.V, c.ldv, vt, pr, nq, c.Ts[b], c.skip1[b], c.skip2[b], work);
+  SVDJ_LAUNCH_CHECK();
+  return 0;
+}
+
 template <typename T, int W>
 static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
   const int b = s & 1;
@@ -3323,24 +3372,14 @@ static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
         set_error("quad steps run the split-bf16 apply (mma 1 or 2), got %d", mma);
         return -3;
       }
-      // T-stationary persistent apply (apply_quad_ts_kernel)
-      const int nq = c.P / 2, at = c.m_pad / 32, vt = c.V ? c.n_v / 32 : 0;
-      uint32_t* work = metric ? metric + 6 : nullptr;
       // cheap k halves: |T - I| <= 2^-7 (A/B only: SVDJ_DEBUG cheap_log2, svdj_debug.h)
       static const float cheap_tol = ldexpf(1.0f, -svdj_debug_knob("cheap_log2", 7));
       // persistent grid (A/B override: SVDJ_DEBUG apply_grid)
       static const int grid_knob = svdj_debug_knob("apply_grid", 0);
-      const int grid = grid_knob > 0 ? grid_knob : c.shared ? quad_ts_grid_shared(nq) : kQuadTsGrid;
-      if (mma == 1)
-        hipLaunchKernelGGL((apply_quad_ts_kernel<3>), dim3(grid), dim3(kQuadTsThreads), 0,
-                           c.st, c.A, c.lda, at, c.V, c.ldv, vt, pr, nq, c.Ts[b], c.skip1[b],
-                           c.skip2[b], work, cheap_tol);
-      else
-        hipLaunchKernelGGL((apply_quad_ts_kernel<2>), dim3(grid), dim3(kQuadTsThreads), 0,
-                           c.st, c.A, c.lda, at, c.V, c.ldv, vt, pr, nq, c.Ts[b], c.skip1[b],
-                           c.skip2[b], work);
-      SVDJ_LAUNCH_CHECK();
-      return 0;
+      const int grid =
+          grid_knob > 0 ? grid_knob : c.shared ? quad_ts_grid_shared(c.P / 2) : kQuadTsGrid;
+      return launch_quad_apply(c, s, mma == 1 ? 3 : 2, grid, cheap_tol,
+                               metric ? metric + 6 : nullptr);
     } else {
       set_error("quad steps need fp32 data and W = 64");
       return -3;
@@ -3349,14 +3388,11 @@ static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
   const dim3 grid(c.P, c.g.a_chunks + ych);
   if constexpr (sizeof(T) == 4) {
     if (mma == 1 || mma == 2) {
-      if (mma == 1)
-        hipLaunchKernelGGL((apply_split_kernel<W, 3>), grid, dim3(kApplyThreads), 0, c.st, c.A,
-                           c.lda, c.g.a_chunks, c.g.rows_a, c.m_pad, c.V, c.ldv, c.g.rows_v, nv,
-                           pr, c.Qb[b], c.skipb[b], (stream_order() >> 1) & 1);
-      else
-        hipLaunchKernelGGL((apply_split_kernel<W, 2>), grid, dim3(kApplyThreads), 0, c.st, c.A,
-                           c.lda, c.g.a_chunks, c.g.rows_a, c.m_pad, c.V, c.ldv, c.g.rows_v, nv,
-                           pr, c.Qb[b], c.skipb[b], (stream_order() >> 1) & 1);
+      with_parts(mma == 2 ? 2 : 3, [&](auto np) {
+        hipLaunchKernelGGL((apply_split_kernel<W, decltype(np)::value>), grid, dim3(kApplyThreads),
+                           0, c.st, c.A, c.lda, c.g.a_chunks, c.g.rows_a, c.m_pad, c.V, c.ldv,
+                           c.g.rows_v, nv, pr, c.Qb[b], c.skipb[b], (stream_order() >> 1) & 1);
+      });
       SVDJ_LAUNCH_CHECK();
       return 0;
     }
@@ -3392,6 +3428,18 @@ static int block_steps_t(const Chain<T>& c, double tol, int absmode, int max_inn
   return 0;
 }
 
+// f(T{}, w) for the data type (0 fp32, 1 fp64) and block width, the width as
+// a compile-time constant (decltype(w)::value); -3 for any other pair.
+template <typename F>
+static int dispatch_tw(int dtype, int W, F&& f) {
+  if (dtype == 0 && W == 32) return f(float{}, std::integral_constant<int, 32>{});
+  if (dtype == 0 && W == 64) return f(float{}, std::integral_constant<int, 64>{});
+  if (dtype == 1 && W == 32) return f(double{}, std::integral_constant<int, 32>{});
+  if (dtype == 1 && W == 64) return f(double{}, std::integral_constant<int, 64>{});
+  set_error("unsupported (dtype=%d, W=%d); supported: W in {32, 64}", dtype, W);
+  return -3;
+}
+
 }  // namespace svdj
 
 using namespace svdj;
@@ -3413,7 +3461,8 @@ extern "C" int svdj_choose_inner_order(int dtype, int W, int pairs) {
 extern "C" int svdj_choose_mma(int dtype, int W) { return (dtype == 0 && W == 64) ? 1 : 0; }
 
 extern "C" size_t svdj_block_workspace_bytes(int dtype, int W, int P, int m_pad, int quad) {
-  return ws_bytes_for(dtype == 1 ? 8 : 4, W, P, m_pad, quad != 0);
+  return dtype == 1 ? solve_ws_bytes<double>(W, P, m_pad, quad != 0)
+                    : solve_ws_bytes<float>(W, P, m_pad, quad != 0);
 }
 
 static int check_dims(int m_pad, int lda, const void* V, int n_v, int ldv, int mma) {
@@ -3465,16 +3514,11 @@ extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, v
     return -2;
   }
   if (P <= 0 || steps < 0) return 0;
-#define SVDJ_STEPS_ARGS                                                                       \
-  m_pad, A, lda, V, n_v, ldv, D, pairs, P, steps, modes, tol, tol_mode, max_inner, ws, ws_bytes, \
-      metric, mma, stream
-  if (dtype == 0 && W == 32) return steps_dispatch<float, 32>(SVDJ_STEPS_ARGS);
-  if (dtype == 0 && W == 64) return steps_dispatch<float, 64>(SVDJ_STEPS_ARGS);
-  if (dtype == 1 && W == 32) return steps_dispatch<double, 32>(SVDJ_STEPS_ARGS);
-  if (dtype == 1 && W == 64) return steps_dispatch<double, 64>(SVDJ_STEPS_ARGS);
-#undef SVDJ_STEPS_ARGS
-  set_error("unsupported (dtype=%d, W=%d); supported: W in {32, 64}", dtype, W);
-  return -3;
+  return dispatch_tw(dtype, W, [&](auto t, auto w) {
+    return steps_dispatch<decltype(t), decltype(w)::value>(
+        m_pad, A, lda, V, n_v, ldv, D, pairs, P, steps, modes, tol, tol_mode, max_inner, ws,
+        ws_bytes, metric, mma, stream);
+  });
 }
 
 extern "C" int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,
@@ -3543,7 +3587,8 @@ extern "C" int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, v
 }
 
 // Cross Gram alone (tests / kernel A/B): slabs (P x nchunk x W x W) of
-// A_bi^T A_bj for the device pair list, with the given row chunking.
+// A_bi^T A_bj for the device pair list, with the given row chunking, through
+// launch_gram (fp32 only).
 extern "C" int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_pad,
                                const int32_t* pairs, int P, int rows_per_chunk, void* slabs,
                                void* stream) {
@@ -3552,34 +3597,27 @@ extern "C" int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_p
     set_error("svdj_gram_cross: bad m_pad/lda/P/rows %d/%d/%d/%d", m_pad, lda, P, rows_per_chunk);
     return -2;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const int nchunk = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
-  if (dtype == 0 && W == 64) {
-    if (lda % 4) {
-      set_error("svdj_gram_cross: lda %d must be a multiple of 4", lda);
-      return -2;
-    }
-    hipLaunchKernelGGL((gram_cross_f32_kernel<GRAM_CROSS>), dim3(P, nchunk, 1), dim3(kGramThreads),
-                       0, st, (const float*)A, lda, m_pad, pairs, rows_per_chunk, (float*)slabs, 0);
-  } else if (dtype == 0 && W == 32) {
-    hipLaunchKernelGGL((gram_kernel<float, 32, GRAM_CROSS>), dim3(P, nchunk, 1), dim3(kGramThreads),
-                       0, st, (const float*)A, lda, m_pad, pairs, rows_per_chunk, (float*)slabs);
-  } else {
+  if (dtype != 0 || (W != 32 && W != 64)) {
     set_error("svdj_gram_cross: unsupported dtype=%d W=%d", dtype, W);
     return -3;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("svdj_gram_cross launch: %s", hipGetErrorString(e));
-    return -101;
+  if (W == 64 && lda % 4) {
+    set_error("svdj_gram_cross: lda %d must be a multiple of 4", lda);
+    return -2;
   }
-  return 0;
+  Chain<float> c{};  // the fields launch_gram reads
+  c.A = const_cast<float*>((const float*)A);  // only read by the Gram
+  c.lda = lda; c.m_pad = m_pad; c.pairs = pairs; c.P = P; c.st = (hipStream_t)stream;
+  c.g.grows = rows_per_chunk;
+  c.g.gchunks = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
+  c.slabs = (float*)slabs;
+  return W == 64 ? launch_gram<float, 64>(c, 0, 0) : launch_gram<float, 32>(c, 0, 0);
 }
 
 // The six cross Grams of a quad step (fp32, W = 64) alone (tests / kernel
 // A/B): pairs = the step's P pairs in quad order ((a,c),(b,d) per quad);
 // slabs (3P x nchunk x W x W): [0, P) the pairs' Grams, then C_ad, C_bc, C_ab,
-// C_cd of every quad (gram_quad_kernel).
+// C_cd of every quad (gram_quad_kernel through launch_quad_gram).
 extern "C" int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* pairs, int P,
                               int rows_per_chunk, void* slabs, int parts, void* stream) {
   if (m_pad <= 0 || m_pad % SVDJ_ROW_ALIGN || lda < m_pad || lda % 4 || P <= 0 || P % 2 ||
@@ -3588,21 +3626,14 @@ extern "C" int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* 
               rows_per_chunk, parts);
     return -2;
   }
-  const int nchunk = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
-  if (parts == 2)
-    hipLaunchKernelGGL((gram_quad_kernel<0, 2>), dim3(P / 2, nchunk), dim3(kGramQThreads), 0,
-                       (hipStream_t)stream, (const float*)A, lda, m_pad, pairs, P, rows_per_chunk,
-                       (float*)slabs);
-  else
-    hipLaunchKernelGGL((gram_quad_kernel<0, 3>), dim3(P / 2, nchunk), dim3(kGramQThreads), 0,
-                       (hipStream_t)stream, (const float*)A, lda, m_pad, pairs, P, rows_per_chunk,
-                       (float*)slabs);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("svdj_gram_quad launch: %s", hipGetErrorString(e));
-    return -101;
-  }
-  return 0;
+  Chain<float> c{};  // the fields launch_quad_gram reads
+  c.A = const_cast<float*>((const float*)A);  // only read by the Gram
+  c.lda = lda; c.m_pad = m_pad; c.pairs = pairs; c.P = P; c.st = (hipStream_t)stream;
+  c.g.qgrows = rows_per_chunk;
+  c.g.qgch = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
+  c.gram_np = parts;
+  c.qslabs = (float*)slabs;
+  return launch_quad_gram<float, 64>(c, 0);
 }
 
 // The quad step's apply alone (tests / kernel A/B): [a b c d] <- [a b c d] T
@@ -3610,7 +3641,7 @@ extern "C" int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* 
 // (2 nq pairs in quad order (a,c),(b,d)), T - I given split into np bf16
 // parts in the ts_frag layout; skip1 / skip2 (2 nq flags each): a quad is
 // skipped when all four of its flags are set.  apply_quad_ts_kernel<np> on
-// `grid` workgroups, launched as launch_apply does; cheap_tol = 2^-cheap_log2;
+// `grid` workgroups through launch_quad_apply; cheap_tol = 2^-cheap_log2;
 // work (device uint32[2], or NULL): the kernel's work counters, accumulated.
 extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, int ldv,
                                const int32_t* pairs, int nq, const void* Ts,
@@ -3628,22 +3659,13 @@ extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, in
               nq, cheap_log2);
     return -2;
   }
-  const int at = m_pad / 32, vt = V ? n_v / 32 : 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (np == 3)
-    hipLaunchKernelGGL((apply_quad_ts_kernel<3>), dim3(grid), dim3(kQuadTsThreads), 0, st,
-                       (float*)A, lda, at, (float*)V, ldv, vt, pairs, nq, (const bf16x8*)Ts, skip1,
-                       skip2, work, ldexpf(1.0f, -cheap_log2));
-  else
-    hipLaunchKernelGGL((apply_quad_ts_kernel<2>), dim3(grid), dim3(kQuadTsThreads), 0, st,
-                       (float*)A, lda, at, (float*)V, ldv, vt, pairs, nq, (const bf16x8*)Ts, skip1,
-                       skip2, work);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("svdj_apply_quad launch: %s", hipGetErrorString(e));
-    return -101;
-  }
-  return 0;
+  Chain<float> c{};  // the fields launch_quad_apply reads
+  c.A = (float*)A; c.lda = lda; c.m_pad = m_pad; c.V = (float*)V; c.n_v = n_v; c.ldv = ldv;
+  c.pairs = pairs; c.P = 2 * nq; c.st = (hipStream_t)stream;
+  c.Ts[0] = const_cast<bf16x8*>((const bf16x8*)Ts);  // T and the flags are only read
+  c.skip1[0] = const_cast<int32_t*>(skip1);
+  c.skip2[0] = const_cast<int32_t*>(skip2);
+  return launch_quad_apply(c, 0, np, grid, ldexpf(1.0f, -cheap_log2), work);
 }
 
 // The middle of a single step alone (tests): launch_evd -- what a step of
@@ -3656,65 +3678,40 @@ extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, in
 //   skip    out, int32 [P]
 //   ws      svdj_evd_alone_workspace_bytes: the slab area of a step with
 //           nchunk row chunks, the rotation records and the step counts
-static size_t evd_alone_bytes(int esize, int W, int P, int nchunk) {
-  return rup256((size_t)P * nchunk * 4 * W * W * esize) +
-         rup256((size_t)P * kCrossMaxInner * W * W * esize) + rup256((size_t)P * sizeof(int32_t));
-}
 extern "C" size_t svdj_evd_alone_workspace_bytes(int dtype, int W, int P, int nchunk) {
   if ((dtype != 0 && dtype != 1) || (W != 32 && W != 64) || P < 1 || nchunk < 1) return 0;
-  return evd_alone_bytes(dtype == 1 ? 8 : 4, W, P, nchunk);
-}
-
-template <typename T, int W>
-static int evd_alone_t(int mode, const void* slabs, int nchunk, void* D, const int32_t* pairs, int P,
-                       double tol, int tol_mode, int max_inner, void* Q, int32_t* skip, void* ws,
-                       uint32_t* metric, hipStream_t st) {
-  Chain<T> c{};
-  c.P = P;
-  c.steps = 1;
-  c.D = (T*)D;
-  c.pairs = pairs;
-  c.st = st;
-  c.g.gchunks = nchunk;
-  char* w = (char*)ws;
-  c.slabs = (T*)w;
-  w += rup256((size_t)P * nchunk * 4 * W * W * sizeof(T));
-  c.rec = (T*)w;
-  w += rup256((size_t)P * kCrossMaxInner * W * W * sizeof(T));
-  c.nsteps = (int32_t*)w;
-  c.Qb[0] = (T*)Q;
-  c.skipb[0] = skip;
-  const size_t in_bytes = (size_t)P * nchunk * (mode == 1 ? 4 : 1) * W * W * sizeof(T);
-  SVDJ_HIP_CHECK(hipMemcpyAsync(c.slabs, slabs, in_bytes, hipMemcpyDeviceToDevice, st));
-  return launch_evd<T, W>(c, 0, mode, tol, tol_mode, max_inner, metric);
+  return dtype == 1 ? evd_alone_ws_bytes<double>(W, P, nchunk)
+                    : evd_alone_ws_bytes<float>(W, P, nchunk);
 }
 
 extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int nchunk, void* D,
                               const int32_t* pairs, int P, double tol, int tol_mode, int max_inner,
                               void* Q, int32_t* skip, void* ws, size_t ws_bytes, uint32_t* metric,
                               void* stream) {
-  if ((dtype != 0 && dtype != 1) || (W != 32 && W != 64)) {
-    set_error("svdj_evd_alone: unsupported dtype=%d W=%d", dtype, W);
-    return -3;
-  }
-  if (mode < 0 || mode > 3 || P < 1 || nchunk < 1 || max_inner < 0 || (tol_mode != 0 && tol_mode != 1) ||
-      !slabs || !D || !pairs || !Q || !skip || !ws || !metric) {
-    set_error("svdj_evd_alone: bad mode/P/nchunk/max_inner/tol_mode %d/%d/%d/%d/%d or a null pointer",
-              mode, P, nchunk, max_inner, tol_mode);
-    return -2;
-  }
-  const size_t need = evd_alone_bytes(dtype == 1 ? 8 : 4, W, P, nchunk);
-  if (ws_bytes < need) {
-    set_error("svdj_evd_alone: workspace too small: %zu < %zu", ws_bytes, need);
-    return -2;
-  }
-#define SVDJ_EVD_ALONE_ARGS \
-  mode, slabs, nchunk, D, pairs, P, tol, tol_mode, max_inner, Q, skip, ws, metric, (hipStream_t)stream
-  if (dtype == 0 && W == 32) return evd_alone_t<float, 32>(SVDJ_EVD_ALONE_ARGS);
-  if (dtype == 0 && W == 64) return evd_alone_t<float, 64>(SVDJ_EVD_ALONE_ARGS);
-  if (W == 32) return evd_alone_t<double, 32>(SVDJ_EVD_ALONE_ARGS);
-  return evd_alone_t<double, 64>(SVDJ_EVD_ALONE_ARGS);
-#undef SVDJ_EVD_ALONE_ARGS
+  return dispatch_tw(dtype, W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W_ = decltype(w)::value;
+    if (mode < 0 || mode > 3 || P < 1 || nchunk < 1 || max_inner < 0 ||
+        (tol_mode != 0 && tol_mode != 1) || !slabs || !D || !pairs || !Q || !skip || !ws ||
+        !metric) {
+      set_error("svdj_evd_alone: bad mode/P/nchunk/max_inner/tol_mode %d/%d/%d/%d/%d or a null "
+                "pointer", mode, P, nchunk, max_inner, tol_mode);
+      return -2;
+    }
+    Chain<T> c{};  // the fields launch_evd reads
+    c.P = P; c.steps = 1; c.D = (T*)D; c.pairs = pairs; c.st = (hipStream_t)stream;
+    c.g.gchunks = nchunk;
+    c.Qb[0] = (T*)Q;
+    c.skipb[0] = skip;
+    const size_t need = evd_alone_layout(c, ws, W_);
+    if (ws_bytes < need) {
+      set_error("svdj_evd_alone: workspace too small: %zu < %zu", ws_bytes, need);
+      return -2;
+    }
+    const size_t in_bytes = (size_t)P * nchunk * (mode == 1 ? 4 : 1) * W_ * W_ * sizeof(T);
+    SVDJ_HIP_CHECK(hipMemcpyAsync(c.slabs, slabs, in_bytes, hipMemcpyDeviceToDevice, c.st));
+    return launch_evd<T, W_>(c, 0, mode, tol, tol_mode, max_inner, metric);
+  });
 }
 
 // The middle of a quad step alone (tests; fp32, W = 64): launch_quad_chain --
@@ -3729,13 +3726,10 @@ extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int
 //           out, int32 [P] each
 //   ws      svdj_quad_chain_workspace_bytes: the chunk sums, the rotation
 //           records and the step counts
-static size_t quad_chain_bytes(int P) {
-  return rup256((size_t)3 * P * 64 * 64 * sizeof(float)) +
-         rup256((size_t)P * kCrossMaxInner * 64 * 64 * sizeof(float)) +
-         rup256((size_t)P * sizeof(int32_t));
-}
 extern "C" size_t svdj_quad_chain_workspace_bytes(int P) {
-  return P < 2 || P % 2 ? 0 : quad_chain_bytes(P);
+  Chain<float> c{};
+  c.P = P;
+  return P < 2 || P % 2 ? 0 : quad_chain_layout(c, nullptr);
 }
 
 extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int32_t* pairs, int P,
@@ -3749,26 +3743,17 @@ extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int
               P, nchunk, max_inner, tol_mode, np);
     return -2;
   }
-  if (ws_bytes < quad_chain_bytes(P)) {
-    set_error("svdj_quad_chain: workspace too small: %zu < %zu", ws_bytes, quad_chain_bytes(P));
+  static const int32_t modes[2] = {4, 5};
+  Chain<float> c{};  // the fields launch_quad_chain reads
+  c.P = P; c.steps = 2; c.D = (float*)D; c.pairs = pairs; c.modes = modes;
+  c.st = (hipStream_t)stream;
+  const size_t need = quad_chain_layout(c, ws);
+  if (ws_bytes < need) {
+    set_error("svdj_quad_chain: workspace too small: %zu < %zu", ws_bytes, need);
     return -2;
   }
-  static const int32_t modes[2] = {4, 5};
-  Chain<float> c{};
-  c.P = P;
-  c.steps = 2;
-  c.D = (float*)D;
-  c.pairs = pairs;
-  c.modes = modes;
-  c.st = (hipStream_t)stream;
   c.g.qgch = nchunk;
   c.qslabs = const_cast<float*>((const float*)slabs);  // only read after the Gram
-  char* w = (char*)ws;
-  c.qred = (float*)w;
-  w += rup256((size_t)3 * P * 64 * 64 * sizeof(float));
-  c.rec = (float*)w;
-  w += rup256((size_t)P * kCrossMaxInner * 64 * 64 * sizeof(float));
-  c.nsteps = (int32_t*)w;
   c.T1 = (double*)T1;
   c.upd = (float*)upd;
   c.Ts[0] = (bf16x8*)Ts;
@@ -3780,7 +3765,8 @@ extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int
 
 // Test/diagnostic hook: X <- X Q for ONE column-block pair (blocks 0 and 1 of
 // X, 2W columns with leading dimension ld, rows padded to SVDJ_ROW_ALIGN),
-// Q row-major 2W x 2W on the device, with the given matrix-core mode.
+// Q row-major 2W x 2W on the device, with the given matrix-core mode: a
+// one-pair step of 512-row chunks through launch_apply.
 extern "C" int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld, const void* Q,
                             void* stream) {
   if (rows <= 0 || rows % SVDJ_ROW_ALIGN || ld < rows) {
@@ -3794,46 +3780,21 @@ extern "C" int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld
   SVDJ_HIP_CHECK(hipMallocAsync((void**)&dbuf, 3 * sizeof(int32_t), st));
   SVDJ_HIP_CHECK(hipMemcpyAsync(dbuf, hpair, 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SVDJ_HIP_CHECK(hipMemcpyAsync(dbuf + 2, hskip, sizeof(int32_t), hipMemcpyHostToDevice, st));
-  const int rows_chunk = 512, chunks = (rows + rows_chunk - 1) / rows_chunk;
-  const dim3 grid(1, chunks), blk(kApplyThreads);
-  int rc = 0;
-  if (dtype == 0 && mma == 1 && W == 64)
-    hipLaunchKernelGGL((apply_split_kernel<64, 3>), grid, blk, 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2, 0);
-  else if (dtype == 0 && mma == 1 && W == 32)
-    hipLaunchKernelGGL((apply_split_kernel<32, 3>), grid, blk, 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2, 0);
-  else if (dtype == 0 && mma == 2 && W == 64)
-    hipLaunchKernelGGL((apply_split_kernel<64, 2>), grid, blk, 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2, 0);
-  else if (dtype == 0 && mma == 2 && W == 32)
-    hipLaunchKernelGGL((apply_split_kernel<32, 2>), grid, blk, 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2, 0);
-  else if (dtype == 0 && mma == 0 && W == 64)
-    hipLaunchKernelGGL((apply_kernel<float, 64>), grid, dim3(apply_threads<float, 64>()), 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2);
-  else if (dtype == 0 && mma == 0 && W == 32)
-    hipLaunchKernelGGL((apply_kernel<float, 32>), grid, blk, 0, st, (float*)X, ld, chunks,
-                       rows_chunk, rows, (float*)nullptr, 0, 0, 0, dbuf, (const float*)Q, dbuf + 2);
-  else if (dtype == 1 && mma == 0 && W == 32)
-    hipLaunchKernelGGL((apply_kernel<double, 32>), grid, blk, 0, st, (double*)X, ld, chunks,
-                       rows_chunk, rows, (double*)nullptr, 0, 0, 0, dbuf, (const double*)Q,
-                       dbuf + 2);
-  else if (dtype == 1 && mma == 0 && W == 64)
-    hipLaunchKernelGGL((apply_kernel<double, 64>), grid, dim3(apply_threads<double, 64>()), 0, st, (double*)X, ld, chunks,
-                       rows_chunk, rows, (double*)nullptr, 0, 0, 0, dbuf, (const double*)Q,
-                       dbuf + 2);
-  else {
+  int rc = -3;
+  if (mma < 0 || mma > 2 || (dtype == 1 && mma != 0))
     set_error("svdj_apply_q: unsupported dtype=%d W=%d mma=%d", dtype, W, mma);
-    rc = -3;
-  }
-  if (rc == 0) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("svdj_apply_q launch: %s", hipGetErrorString(e));
-      rc = -101;
-    }
-  }
+  else
+    rc = dispatch_tw(dtype, W, [&](auto t, auto w) {
+      using T = decltype(t);
+      // the fields launch_apply reads (no modes: mode 0; no V: A's row chunks only)
+      Chain<T> c{};
+      c.A = (T*)X; c.lda = ld; c.m_pad = rows; c.pairs = dbuf; c.P = 1; c.st = st;
+      c.g.rows_a = 512;
+      c.g.a_chunks = (rows + c.g.rows_a - 1) / c.g.rows_a;
+      c.Qb[0] = const_cast<T*>((const T*)Q);  // only read by the apply
+      c.skipb[0] = dbuf + 2;
+      return launch_apply<T, decltype(w)::value>(c, 0, mma, nullptr);
+    });
   (void)hipFreeAsync(dbuf, st);
   return rc;
 }

@@ -348,6 +348,47 @@ def test_gram_cross_matches_reference(svdj, cuda, W, m, m_pad, rows):
         assert (got[p] - ref).abs().max().item() < 2e-6 * scale * math.sqrt(m / 100)
 
 
+@pytest.mark.parametrize("skip_one", [False, True])
+@pytest.mark.parametrize("W,mode,mma", [(32, 2, "native"), (64, 3, "native"), (64, 3, "bf16x6")])
+def test_single_step_equals_its_hooks(svdj, cuda, W, mode, mma, skip_one):
+    """A step of block_steps is, bit for bit, gram_cross -> evd_alone ->
+    apply_q per rotated pair: the hooks run the solve's launchers.  4 blocks,
+    2 pairs, m_pad = 128: the step's geometry is one 128-row Gram chunk and
+    one apply chunk (block.hip make_geometry), which the hooks are given.
+    U(0, 1) columns, so the pairs rotate; ``skip_one``: pair (1, 2) lives on
+    disjoint rows (a zero cross Gram), so its skip flag is set."""
+    K = svdj.ops.kernels
+    nb, m_pad, P, tol, inner = 4, 128, 2, 1e-6, 2
+    A = torch.rand(nb * W, m_pad, generator=torch.Generator().manual_seed(11 + W))
+    if skip_one:
+        A[W:2 * W, 64:] = 0
+        A[2 * W:3 * W, :64] = 0
+    pairs = torch.tensor([[0, 3], [1, 2]], dtype=torch.int32, device=cuda)
+    A0 = A.to(cuda)
+    D0 = K.col_norms2(A0, m_pad)
+    A1, D1 = A0.clone(), D0.clone()
+    K.block_steps(A1, None, D1, m_pad, pairs[None], W, [mode], tol, inner, K.new_metric(cuda),
+                  mma=mma)
+    # the step's skip flags: skipb[0] of its workspace, behind the slab area
+    # and the two Q buffers, here P x 2W x 2W fp32 each (block.hip solve_layout)
+    ws = K.block_workspace(torch.float32, W, P, m_pad, A1.device)
+    off = 3 * P * 4 * W * W * 4
+    skip1 = ws[off:off + 4 * P].view(torch.int32).clone()
+    A2, D2 = A0.clone(), D0.clone()
+    slabs = K.gram_cross(A2, m_pad, pairs, W, 128)
+    Q, skip2 = K.evd_alone(slabs, D2, pairs, W, mode, tol, inner, K.new_metric(cuda))
+    for p, (bi, bj) in enumerate(pairs.tolist()):
+        if int(skip2[p]):
+            continue
+        rows = list(range(bi * W, (bi + 1) * W)) + list(range(bj * W, (bj + 1) * W))
+        X = A2[rows].contiguous()
+        K.apply_q(X, Q[p], W, mma=mma)
+        A2[rows] = X
+    assert skip2.tolist() == [0, int(skip_one)] and torch.equal(skip1, skip2)
+    assert torch.equal(D1, D2)
+    assert torch.equal(A1, A2) and not torch.equal(A1[:W], A0[:W])
+
+
 @pytest.mark.parametrize("scale", [1.0, 1e-16, 2.0 ** 40])
 def test_block_solve_is_scale_invariant_gpu(svdj, cuda, scale):
     """c A solves like A on the GPU kernels (the negligible-column floor is

@@ -398,6 +398,33 @@ def test_quad_step_two_part_gram(svdj, cuda):
     assert float((A64[:, :m].t() @ v.t() - a.double()[:, :m].t()).abs().max()) < 2e-5
 
 
+@pytest.mark.parametrize("parts", [3, 2])
+def test_quad_step_equals_its_hooks(svdj, cuda, parts):
+    """A quad step of block_steps is, bit for bit, gram_quad -> quad_chain ->
+    apply_quad: the hooks run the solve's launchers.  One quad, m_pad = n_v =
+    256: the step's Gram takes 2 chunks of 128 rows, unsummed (block.hip
+    quad_geometry), and its apply 256 workgroups with cheap halves below 2^-7
+    (launch_apply), which the hooks are given.  ``parts``: of the quad Gram."""
+    K = svdj.ops.kernels
+    W, nb, m, m_pad, tol = 64, 4, 250, 256, 1e-6
+    A0 = _orth_blocks(nb, W, m, m_pad, seed=21).float().to(cuda)
+    V0 = torch.zeros(nb * W, nb * W, dtype=torch.float32, device=cuda)
+    K.set_identity(V0, nb * W)
+    D0 = K.col_norms2(A0, m_pad)
+    pairs = _quad_pairs(svdj, nb).to(cuda)
+    A1, V1, D1 = A0.clone(), V0.clone(), D0.clone()
+    K.block_steps(A1, V1, D1, m_pad, pairs, W, [4, 5], tol, 1, K.new_metric(cuda), mma="bf16x6",
+                  gram_parts=parts)
+    A2, V2, D2 = A0.clone(), V0.clone(), D0.clone()
+    slabs = K.gram_quad(A2, m_pad, pairs[0], W, 128, parts=parts)
+    ch = K.quad_chain(slabs, D2, pairs[0], pairs[1], tol, 1, K.new_metric(cuda), np=3)
+    K.apply_quad(A2, V2, m_pad, pairs[0], ch["Ts"], ch["skip1"], ch["skip2"], np=3, grid=256,
+                 cheap_log2=7)
+    assert int(ch["skip1"].sum()) == 0 and not torch.equal(A1, A0)
+    assert torch.equal(D1, D2)
+    assert torch.equal(A1, A2) and torch.equal(V1, V2)
+
+
 def test_quad_step_mixed_converged_and_coupled(svdj, cuda):
     """4 quads in a step, two of them orthonormal 256-column panels: the
     reference's rotated-pair count, and the converged quads' A, V, D bitwise
