@@ -37,6 +37,10 @@ void set_error(const char* fmt, ...);
     }                                                                          \
   } while (0)
 
+// ------------------- shared by the block kernels and the workspace layouts
+__host__ __device__ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
+constexpr int kCrossMaxInner = 4;  // inner sweeps whose rotation records fit the workspace
+
 // ------------------------------------------------------------ wave helpers
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
@@ -84,6 +88,7 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f64x2 = __attribute__((ext_vector_type(2))) double;
 using f64x4 = __attribute__((ext_vector_type(4))) double;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 template <typename T>
 struct Mfma;

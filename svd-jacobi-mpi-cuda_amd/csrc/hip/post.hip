@@ -140,7 +140,7 @@ extern "C" int svdj_col_norms2(int dtype, const void* A, int m_pad, int lda, int
 }
 
 // metric[2..3] (a double) = the negligible-column floor of the block EVDs
-// (block.hip needs_rotation).  svdj_norm_floor_value is its scale-relative
+// (block_evd.hpp needs_rotation).  svdj_norm_floor_value is its scale-relative
 // factor m realmin / eps (times the largest squared column norm, see
 // svdj_set_norm_floor_scaled).
 __global__ void norm_floor_kernel(double v, uint32_t* __restrict__ metric) {

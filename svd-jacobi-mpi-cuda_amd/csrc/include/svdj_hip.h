@@ -107,7 +107,7 @@ int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, void* V,
 int svdj_reset_metric(uint32_t* metric, void* stream);
 
 // Diagnostic hooks.  Each runs one stage of a step through the launcher a
-// solve calls for it (block.hip launch_*), on buffers given by the caller.
+// solve calls for it (block_launch.hpp launch_*), on buffers given by the caller.
 // Cross Gram slabs (P x nchunk x W x W) of A_bi^T A_bj
 // for a device pair list with the given row chunking (fp32).
 int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_pad,

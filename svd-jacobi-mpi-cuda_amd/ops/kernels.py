@@ -102,7 +102,7 @@ def reset_metric(metric: torch.Tensor):
 
 
 def norm_floor(dtype: torch.dtype, m: int, dmax: float = 1.0) -> float:
-    """Negligible-column floor: the block EVDs (block.hip needs_rotation) do
+    """Negligible-column floor: the block EVDs (block_evd.hpp needs_rotation) do
     not rotate pairs with a squared column norm at or below
     max(m realmin, m realmin / eps * dmax), dmax the largest squared column
     norm of the matrix.  The second term is the round-3 floor m realmin / eps
@@ -299,7 +299,7 @@ INNER_ORDERS = ("cyclic", "bipartite", "cross")
 
 def step_modes(modes, inner_order="cyclic"):
     """Plan modes (0 cross, 1 full) -> kernel modes: with the bipartite inner
-    ordering cross steps become mode 2 (block.hip EVD_BIP, W EVD steps instead
+    ordering cross steps become mode 2 (block_evd.hpp EVD_BIP, W EVD steps instead
     of 2W-1), with the cross-only ordering mode 3 (evd_cross_kernel: the
     bipartite steps tracking only the cross couplings); full steps always use
     the cyclic EVD."""
@@ -389,7 +389,7 @@ def gram_quad(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
     """The six cross Grams of a quad step (fp32, W = 64): ``pairs`` (P, 2) on
     the device in quad order ((a, c), (b, d) per quad).  Returns the slabs
     (3P, nchunk, W, W): the P pairs' Grams, then C_ad, C_bc, C_ab, C_cd of
-    every quad (csrc/hip/block.hip gram_quad_kernel; ``parts`` 2: the
+    every quad (csrc/hip/block_quad.hpp gram_quad_kernel; ``parts`` 2: the
     early-sweep form on 2 bf16 parts)."""
     _check_layout(At, m_pad)
     if At.dtype != torch.float32 or W != 64:
@@ -416,7 +416,7 @@ def apply_q(Xt: torch.Tensor, Q: torch.Tensor, W: int, mma="native"):
 
 def apply_quad(At, Vt, m_pad, pairs, Ts, skip1, skip2, np: int = 3, grid: int = 256,
                cheap_log2: int = 7, work: torch.Tensor | None = None):
-    """The quad step's apply alone (fp32, W = 64; csrc/hip/block.hip
+    """The quad step's apply alone (fp32, W = 64; csrc/hip/block_quad.hpp
     apply_quad_ts_kernel, launched as a quad step launches it): in place
     [a b c d] <- [a b c d] T on At (rows [0, m_pad)) and Vt (all n_v rows, or
     None) for the quads of ``pairs`` (2 nq, 2) in quad order ((a, c), (b, d)).
@@ -473,7 +473,7 @@ def _check_chain_args(what, slabs, D, pairs, metric, nb_of_d):
 
 def evd_alone(slabs, D, pairs, W: int, mode: int, tol: float, max_inner: int, metric,
               tol_mode="relative", Q: torch.Tensor | None = None):
-    """The middle of a single block step alone (csrc/hip/block.hip launch_evd,
+    """The middle of a single block step alone (csrc/hip/block_launch.hpp launch_evd,
     what a step runs after its Gram): ``slabs`` (P, nchunk, W, W), or (P,
     nchunk, 2W, 2W) for ``mode`` 1, device fp32 / fp64 in the layout the Gram
     kernels write; ``D`` squared column norms by block id (updated in place);
@@ -509,7 +509,7 @@ def evd_alone(slabs, D, pairs, W: int, mode: int, tol: float, max_inner: int, me
 
 def quad_chain(slabs, D, pairs0, pairs1, tol: float, max_inner: int, metric, np: int = 3,
                tol_mode="relative"):
-    """The middle of a quad step alone (fp32, W = 64; csrc/hip/block.hip
+    """The middle of a quad step alone (fp32, W = 64; csrc/hip/block_launch.hpp
     launch_quad_chain, what a quad step runs between its Gram and its apply):
     ``slabs`` (3P, nchunk, 64, 64) in :func:`gram_quad`'s order, ``D`` squared
     column norms by block id (updated in place), ``pairs0`` (P, 2) in quad

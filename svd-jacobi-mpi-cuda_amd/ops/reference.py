@@ -75,7 +75,7 @@ def round_robin_pairs(N):
 
 
 def ring_pairs(N):
-    """The cyclic ordering as evd_kernel steps through it (block.hip
+    """The cyclic ordering as evd_kernel steps through it (block_evd.hpp
     ring_slot): at step st slot a pairs player N-1 (a = 0) or the player at
     ring position a-1 with the one at position N-2-a; the player at position x
     after st steps is ((x - st) mod (N-1) + 1) mod (N-1).  The same pairs per
@@ -93,7 +93,7 @@ _RR_CACHE = {}
 
 
 def bipartite_pairs(W):
-    """Cross-pair ordering of the bipartite EVD (block.hip Ord<W, EVD_BIP>):
+    """Cross-pair ordering of the bipartite EVD (block_evd.hpp Ord<W, EVD_BIP>):
     step t pairs local column a of block i with column (a + t) mod W of
     block j (player W + ...), W steps per sweep."""
     return [[(a, W + (a + t) % W) for a in range(W)] for t in range(W)]
@@ -106,7 +106,7 @@ def jacobi_evd(G, tol, max_sweeps, tol_mode: int = 0, order: str = "cyclic", flo
     Same orderings (``cyclic``: circle-method round robin over all pairs;
     ``bipartite``: the cross pairs only; ``cross``: the bipartite steps with
     the within-block couplings held at zero, i.e. only the cross couplings
-    and the diagonal tracked -- block.hip evd_cross_kernel), threshold and
+    and the diagonal tracked -- block_evd.hpp evd_cross_kernel), threshold and
     update formulas as the kernels.  Returns (G_diag_final, Q, rotated);
     with ``stats`` (a dict) the second-order stop test's inputs
     (csrc/include/svdj_stop.h) accumulate: ``smax`` the largest effective

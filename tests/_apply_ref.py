@@ -125,7 +125,7 @@ def dense_quad_t(seed):
 # --------------------------------------------------------------- emulation
 def split_bf16(x, np_):
     """np_ bf16 parts of the fp32 tensor x by successive round-to-nearest-even
-    conversions (block.hip split_bf16)."""
+    conversions (block_apply.hpp split_bf16)."""
     r = x.float().clone()
     parts = []
     for i in range(np_):

@@ -2,7 +2,7 @@
 columns and blocks of [a b c d] unchanged, what each of them claims, and the
 work counter the quad apply must report for them.  Plain torch, CPU.
 
-The quad apply (csrc/hip/block.hip apply_quad_ts_kernel, SPARSE) decides from
+The quad apply (csrc/hip/block_quad.hpp apply_quad_ts_kernel, SPARSE) decides from
 the values of T - I alone: a column whose column of T - I is zero is not
 stored; a wave (32 columns) none of whose columns change runs no product; a
 32-row k block that is zero in a wave's slice is skipped there; a wave whose

@@ -303,7 +303,7 @@ def cross_evd(C, Dx, Dy, tol, max_inner, dtype):
 
 
 def update_products(T1p, M, swap=False, transpose=False, emulate=False):
-    """upd (2 nq, 64, 64) = L^T M R of every quad (block.hip
+    """upd (2 nq, 64, 64) = L^T M R of every quad (block_quad.hpp
     quad_update_kernel): T1p (2 nq, 128, 128) the pairs' (a,c), (b,d)
     transforms, M (nq, 128, 128) = [[C_ab, C_ad], [C_cb, C_cd]] (rows a; c,
     columns b; d); j = 0: Q_ac[:, :64]^T M Q_bd[:, 64:] = C(a', d'), j = 1:

@@ -174,7 +174,7 @@ def test_block_converges_on_reference_triangular_input(svdj):
 
 def test_norm_floor_skips_underflowing_columns(svdj):
     """A pair whose column's squared norm is at or below the underflow floor
-    is not rotated (ops/reference.py mirrors block.hip needs_rotation)."""
+    is not rotated (ops/reference.py mirrors block_evd.hpp needs_rotation)."""
     import torch
     K, R = svdj.ops.kernels, svdj.ops.reference
     assert K.norm_floor(torch.float64, 1000) == 1000 * torch.finfo(torch.float64).tiny / \

@@ -89,7 +89,7 @@ def test_ring_pairs_cover_every_pair_once():
         assert len(steps) == N - 1 and all(s[0][0] == N - 1 for s in steps)
         assert all(sorted(x for pr in s for x in pr) == list(range(N)) for s in steps)
         assert len({(min(a, b), max(a, b)) for s in steps for a, b in s}) == N * (N - 1) // 2
-    assert E.REF.ring_pairs(8)[0] == [(7, 0), (1, 6), (2, 5), (3, 4)]  # first0 / second0 of block.hip
+    assert E.REF.ring_pairs(8)[0] == [(7, 0), (1, 6), (2, 5), (3, 4)]  # first0 / second0 of block_evd.hpp
 
 
 def test_split_chunks_sum_exactly():

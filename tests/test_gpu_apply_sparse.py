@@ -1,5 +1,5 @@
 """The quad apply on transforms that leave columns and blocks unchanged
-(csrc/hip/block.hip apply_quad_ts_kernel, SPARSE), through kernels.apply_quad:
+(csrc/hip/block_quad.hpp apply_quad_ts_kernel, SPARSE), through kernels.apply_quad:
 columns whose column of T - I is zero are not stored, waves that change
 nothing run no product, k blocks that are zero in a wave's slice are skipped,
 and columns that neither change nor feed a product are not loaded.

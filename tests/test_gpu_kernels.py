@@ -276,7 +276,7 @@ def test_fp64_block_widths_end_to_end(svdj, cuda, W):
 @pytest.mark.parametrize("dtype,W", [(torch.float32, 32), (torch.float32, 64),
                                      (torch.float64, 32), (torch.float64, 64)])
 def test_block_step_bipartite_matches_reference(svdj, cuda, dtype, W, order, inner):
-    """Cross step with the bipartite EVD ordering (mode 2, block.hip
+    """Cross step with the bipartite EVD ordering (mode 2, block_evd.hpp
     Ord<W, EVD_BIP>: W steps of the cross pairs, DPP rotate + permlane32 swap
     of the register Q) or the cross-only one (mode 3, evd_cross_kernel: the
     same steps tracking only the cross couplings, transpose-pair updates in
@@ -354,7 +354,7 @@ def test_single_step_equals_its_hooks(svdj, cuda, W, mode, mma, skip_one):
     """A step of block_steps is, bit for bit, gram_cross -> evd_alone ->
     apply_q per rotated pair: the hooks run the solve's launchers.  4 blocks,
     2 pairs, m_pad = 128: the step's geometry is one 128-row Gram chunk and
-    one apply chunk (block.hip make_geometry), which the hooks are given.
+    one apply chunk (block_layout.hpp make_geometry), which the hooks are given.
     U(0, 1) columns, so the pairs rotate; ``skip_one``: pair (1, 2) lives on
     disjoint rows (a zero cross Gram), so its skip flag is set."""
     K = svdj.ops.kernels
@@ -370,7 +370,7 @@ def test_single_step_equals_its_hooks(svdj, cuda, W, mode, mma, skip_one):
     K.block_steps(A1, None, D1, m_pad, pairs[None], W, [mode], tol, inner, K.new_metric(cuda),
                   mma=mma)
     # the step's skip flags: skipb[0] of its workspace, behind the slab area
-    # and the two Q buffers, here P x 2W x 2W fp32 each (block.hip solve_layout)
+    # and the two Q buffers, here P x 2W x 2W fp32 each (block_layout.hpp solve_layout)
     ws = K.block_workspace(torch.float32, W, P, m_pad, A1.device)
     off = 3 * P * 4 * W * W * 4
     skip1 = ws[off:off + 4 * P].view(torch.int32).clone()

@@ -402,7 +402,7 @@ def test_quad_step_two_part_gram(svdj, cuda):
 def test_quad_step_equals_its_hooks(svdj, cuda, parts):
     """A quad step of block_steps is, bit for bit, gram_quad -> quad_chain ->
     apply_quad: the hooks run the solve's launchers.  One quad, m_pad = n_v =
-    256: the step's Gram takes 2 chunks of 128 rows, unsummed (block.hip
+    256: the step's Gram takes 2 chunks of 128 rows, unsummed (block_layout.hpp
     quad_geometry), and its apply 256 workgroups with cheap halves below 2^-7
     (launch_apply), which the hooks are given.  ``parts``: of the quad Gram."""
     K = svdj.ops.kernels

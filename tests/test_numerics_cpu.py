@@ -1,4 +1,4 @@
-"""CPU checks of the split-bf16 apply's arithmetic (csrc/hip/block.hip
+"""CPU checks of the split-bf16 apply's arithmetic (csrc/hip/block_apply.hpp
 apply_split_kernel): the 3-way round-to-nearest bf16 split is accurate to
 2^-27, and the six order < 3 products of X (Q - I), added to X in fp32,
 reproduce X Q to fp32 rounding.  The GPU kernel itself is checked against the

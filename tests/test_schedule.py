@@ -119,7 +119,7 @@ def test_distributed_sweep_covers_every_block_pair_once(P, k):
 
 def test_evd_ring_matches_dpp_movement():
     """The EVD kernel computes slot players arithmetically (ring_slot in
-    csrc/hip/block.hip) for the G updates, while the register Q follows the
+    csrc/hip/block_evd.hpp) for the G updates, while the register Q follows the
     DPP shifts; both must describe the same circle-method movement and cover
     every pair once per N-1 steps."""
     def ring_player(W, pos, st):
@@ -162,7 +162,7 @@ def _pos_next(W, P):
 
 
 def _next_meeting(W, P1, P2):
-    """Python twin of block.hip next_meeting (position R = fixed player)."""
+    """Python twin of block_evd.hpp next_meeting (position R = fixed player)."""
     R = 2 * W - 1
 
     def slot_of(pos):
@@ -321,7 +321,7 @@ def test_evd_position_space_emulation(W):
 
 # ---- bipartite inner ordering (cross steps): X players fixed at positions
 # 0..W-1, the Y player at Y-position p (position W+p) moves to p-1 (mod W)
-# every step; slot a pairs positions (a, W+a).  Python twins of block.hip
+# every step; slot a pairs positions (a, W+a).  Python twins of block_evd.hpp
 # BipOrder, and the same position-space emulation as above.
 def _bip_players(W, a, st):
     return a, W + (a + st) % W

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model and optimiser for the EVD kernel's block dealing.
 
-The LDS EVD (csrc/hip/block.hip, evd_kernel) gives every thread up to
+The LDS EVD (csrc/hip/block_evd.hpp, evd_kernel) gives every thread up to
 MAXOFF off-diagonal slot-pair blocks (a < b) for the whole kernel
 (EvdDeal).  Every step a thread reads the 4 G entries of each block at
 static position-space addresses, reads the two slots' rotation records and
@@ -255,7 +255,7 @@ def header(tables):
            "// Bank-conflict-optimised block dealing of the fp32 EVD (EvdDeal): entry",
            "// j * 1024 + tid = (a << 8) | b of thread tid's j-th slot-pair block, 0xffff",
            "// if none; the first W entries are the duty blocks (checked by",
-           "// evd_deal_ok in block.hip).",
+           "// evd_deal_ok in block_evd.hpp).",
            "#pragma once", "", "namespace svdj {", ""]
     for (W, order), slots in tables.items():
         name = f"kEvdDealF32_W{W}_{'bip' if order == BIP else 'cyc'}"

@@ -1,7 +1,8 @@
 """Measurement-only kernel variants for A/B runs on the GPU box.
 
 Builds a variant of libsvdj_hip.so from a PATCHED COPY of csrc/hip/block.hip
-(the production source never carries experiment switches).  Variants:
+and its block_*.hpp stage headers (the production source never carries
+experiment switches).  Variants:
 
   nogram    the cross-Gram launches of the cross steps are dropped: the EVD
             reads the previous step's slabs (valid Grams of other pairs, so the
@@ -97,12 +98,19 @@ GRAM_LPL = "constexpr int kGramLpl64 = 16;"
 GRAM_DECL = "__global__ __launch_bounds__(kGramThreads) void gram_kernel("
 
 
-def _sub(src: str, old: str, new: str) -> str:
-    assert src.count(old) == 1, f"patch anchor not found once: {old[:60]!r}"
-    return src.replace(old, new)
+def sources() -> dict:
+    """block.hip and its stage headers: file name -> text."""
+    hip = CSRC / "hip"
+    return {f.name: f.read_text() for f in [hip / "block.hip", *sorted(hip.glob("block_*.hpp"))]}
 
 
-def patch(src: str, variant: str) -> str:
+def _sub(src: dict, old: str, new: str) -> dict:
+    """Replace `old`, found exactly once across the files, in the file that holds it."""
+    assert sum(t.count(old) for t in src.values()) == 1, f"patch anchor not found once: {old[:60]!r}"
+    return {name: t.replace(old, new) for name, t in src.items()}
+
+
+def patch(src: dict, variant: str) -> dict:
     if variant in ("nogram", "fused", "fusedl2"):
         src = _sub(src, GRAM_CROSS, GRAM_CROSS.replace("} else {", "} else if (false) {"))
     if variant == "fused":
@@ -133,10 +141,11 @@ def main():
         raise SystemExit("variant: " + " | ".join(VARIANTS))
     scratch = out.parent / f"ab_{variant}"
     scratch.mkdir(parents=True, exist_ok=True)
+    for name, text in patch(sources(), variant).items():
+        (scratch / name).write_text(text)
     blk = scratch / "block.hip"
-    blk.write_text(patch((CSRC / "hip" / "block.hip").read_text(), variant))
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-result",
-             "-Wno-pass-failed", f"-I{CSRC / 'include'}", f"-I{CSRC / 'hip'}"]
+             "-Wno-pass-failed", f"-I{CSRC / 'include'}", f"-I{scratch}", f"-I{CSRC / 'hip'}"]
     objs = []
     for src in (blk, CSRC / "hip" / "post.hip", CSRC / "hip" / "scalar.hip"):
         obj = scratch / (src.stem + ".o")

@@ -5,7 +5,7 @@
 //         -c tools/micro/evd_bench.hip -o evd_bench.o
 //   hipcc --offload-arch=gfx950 evd_bench.o <lib/obj/post.o> -o evd_bench
 //   ./evd_bench P nchunk reps      (prints microseconds per launch)
-#include "block.hip"
+#include "block_evd.hpp"
 
 #include <cstdio>
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// Ablations of the quad apply (apply_quad_ts_kernel, csrc/hip/block.hip) at the
+// Ablations of the quad apply (apply_quad_ts_kernel, csrc/hip/block_quad.hpp) at the
 // headline geometry (development aid, round 6): 16384 rows of A and 16384 of V,
 // 64 active quads (a merged 128-pair quad step of the 16384^2 solve), realistic
 // T - I (entries ~U(-0.01, 0.01), split into 3 RNE bf16 parts).  Variants by the
@@ -14,7 +14,7 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I svd-jacobi-mpi-cuda_amd/csrc/include
 //     -I svd-jacobi-mpi-cuda_amd/csrc/hip -c tools/micro/quad_apply_ab.hip -o qab.o
 //   hipcc --offload-arch=gfx950 qab.o svd-jacobi-mpi-cuda_amd/lib/obj/post.o -o tools/micro/quad_apply_ab
-#include "block.hip"
+#include "block_quad.hpp"
 
 #include <algorithm>
 #include <cstdio>

@@ -1,19 +1,21 @@
-// Host-only check of the workspace layouts of csrc/hip/block.hip (solve_layout,
+// Host-only check of the workspace layouts of csrc/hip/block_layout.hpp (solve_layout,
 // evd_alone_layout, quad_chain_layout) under AddressSanitizer + UBSan: every
 // area of a layout is filled with its own byte inside a heap buffer of exactly
 // the reported size, then read back.  An area that overlaps another reads back
 // wrong; one that runs past the reported size is an ASan heap overflow.  The
 // area sizes are stated here independently of the layout routines.  No kernel
-// is launched and no GPU is needed.
+// is launched and no GPU is needed; the program holds the layout header alone
+// (no kernel, no C entry point, nothing of the library to link).
 //
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined
 //     -Xarch_host -fno-sanitize-recover=undefined -I svd-jacobi-mpi-cuda_amd/csrc/include
 //     -I svd-jacobi-mpi-cuda_amd/csrc/hip tools/micro/ws_layout_check.hip
-//     svd-jacobi-mpi-cuda_amd/csrc/hip/post.hip -o tools/micro/ws_layout_check
-//     -fsanitize=address,undefined
-#include "block.hip"
+//     -o tools/micro/ws_layout_check -fsanitize=address,undefined
+#include "block_layout.hpp"
 
 #include <cstdio>
+#include <cstring>
+#include <vector>
 
 struct Area {
   const char* name;
@@ -101,10 +103,10 @@ int main() {
         n += 2;
       }
   for (int P : {2, 8, 64}) {
-    const size_t size = svdj_quad_chain_workspace_bytes(P);
-    std::vector<char> buf(size);
     svdj::Chain<float> c{};
     c.P = P;
+    const size_t size = svdj::quad_chain_layout(c, nullptr);  // svdj_quad_chain_workspace_bytes
+    std::vector<char> buf(size);
     bad += svdj::quad_chain_layout(c, buf.data()) != size;
     bad += check("quad_chain", {{"qred", c.qred, (size_t)3 * P * 64 * 64 * 4},
                                 {"rec", c.rec, (size_t)P * svdj::kCrossMaxInner * 64 * 64 * 4},
