@@ -1,6 +1,7 @@
 """Public entry points.
 
 ``svd(A)`` -- functional API returning (U, S, V) (V, not V^T).
+``svd_batched(A)`` -- the same for a batch (..., m, n) of small matrices.
 ``gesvd(jobu, jobv, m, n, A, lda, s, V, ldv)`` -- the reference's in-place
 signature (reference main.cu:440-448 ``omp_mpi_cuda_dgesvd_local_matrices``,
 lib/JacobiMethods.cuh:44-62): column-major A (leading dimension lda) is
@@ -13,7 +14,8 @@ from __future__ import annotations
 import torch
 
 from .config import SolverConfig, SVDOptions
-from .models.base import SVDResult, sort_result
+from .models.base import BatchedSVDResult, SVDResult, sort_result
+from .models.batched import BatchedJacobi
 from .models.block import BlockJacobi
 from .models import precondition as pre
 from .models.oracle import OracleJacobi
@@ -73,6 +75,29 @@ def svd(A: torch.Tensor, jobu=SVDOptions.AllVec, jobv=SVDOptions.AllVec,
     if cfg.sort:
         res = sort_result(res)
     return res
+
+
+def svd_batched(A: torch.Tensor, jobu=SVDOptions.AllVec, jobv=SVDOptions.AllVec,
+                config: SolverConfig | None = None, device=None, **overrides) -> BatchedSVDResult:
+    """One-sided Jacobi SVD of every matrix of a batch ``A`` (..., m, n).
+
+    On a GPU, matrices with at most 64 columns (after a wide input is
+    transposed) that fit in a CU's LDS are solved by one launch, one
+    workgroup per matrix (models/batched.py); anything else, and CPU input,
+    runs :func:`svd` per matrix.  ``device``, ``config`` and the keyword
+    overrides are those of :func:`svd` (``tol``, ``max_sweeps``, ``sort``,
+    ``tol_mode``, ``dtype``).  Returns a :class:`BatchedSVDResult` that
+    unpacks as ``U, S, V`` with shapes (..., m, k), (..., k), (..., n, k)."""
+    if not isinstance(A, torch.Tensor) or A.dim() < 3:
+        raise ValueError("svd_batched needs a batch (..., m, n) with A.dim() >= 3; "
+                         "use svd() for a single 2-D matrix")
+    if not A.is_floating_point():
+        raise TypeError(f"svd_batched needs a floating-point tensor, got {A.dtype}")
+    cfg = config or SolverConfig()
+    if overrides:
+        cfg = SolverConfig(**{**cfg.__dict__, **overrides})
+    dev = torch.device(device) if device is not None else A.device
+    return BatchedJacobi(cfg).solve(A, jobu, jobv, device=dev)
 
 
 def gesvd(jobu, jobv, m: int, n: int, A: torch.Tensor, lda: int, s: torch.Tensor,

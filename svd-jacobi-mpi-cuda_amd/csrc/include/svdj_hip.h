@@ -183,6 +183,45 @@ int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int32_t* pairs
                     void* stream);
 
 // ---------------------------------------------------------------------------
+// Batched path (csrc/hip/batched.hip): `batch` independent small SVDs in one
+// launch, one workgroup per matrix, the matrix and V resident in LDS from
+// load to store (scalar one-sided Jacobi, round-robin ordering, the scalar
+// path's rotation test with the block path's underflow floor per matrix,
+// sigma / U finalize fused).  Envelope: m >= n, 1 <= n <= 64, and
+// svdj_batched_lds_bytes(dtype, m, n, V != NULL) != 0.
+//
+// The LDS bytes a workgroup takes for an (m x n) matrix, from the layout
+// routine the kernel carves its LDS with; 0: outside the envelope or above
+// the 163840-byte cap (a CU's whole LDS).
+size_t svdj_batched_lds_bytes(int dtype, int m, int n, int want_v);
+// Threads of the workgroup that solves a matrix of n columns (8 lanes per
+// column pair of a step, rounded up to whole waves); 0 for n outside [1, 64].
+int svdj_batched_threads(int n);
+// The solve:
+//   A       device, read in place through element strides: matrix b, row i,
+//           column j at A[b sb + i sr + j sc] (loads are coalesced when sc or
+//           sr is 1: a contiguous (batch, m, n) tensor, or the transposed
+//           view of a contiguous (batch, n, m) one)
+//   U       out, contiguous (batch, m, n) row-major, or NULL: not computed
+//   S       out, contiguous (batch, n), unsorted
+//   V       out, contiguous (batch, n, n) row-major (V, not V^T), or NULL:
+//           not accumulated and no LDS taken for it
+//   tol, tol_mode  as svdj_scalar_step (the absolute test is on the caller's
+//           matrix, whatever the kernel's internal scaling); in both modes a
+//           pair with a squared norm at or below the underflow floor is not
+//           rotated; a matrix stops after a sweep that rotated nothing, or
+//           after max_sweeps sweeps
+//   sweeps  out, device int32 [batch]: sweeps run per matrix
+//   off     out, device float [batch]: largest |a_p.a_q| / (|a_p| |a_q|) seen
+//           in the matrix's last sweep
+// Returns 0; -2 with the error string set and nothing launched on a bad
+// argument (bad dtype, m < n, n > 64, does not fit in LDS, max_sweeps < 0,
+// NULL A / S / sweeps / off); batch == 0 returns 0 without any HIP call.
+int svdj_batched_svd(int dtype, int batch, int m, int n, const void* A, long sb, long sr,
+                     long sc, void* U, void* S, void* V, double tol, int tol_mode,
+                     int max_sweeps, int32_t* sweeps, float* off, void* stream);
+
+// ---------------------------------------------------------------------------
 // Post-processing / utilities.
 // V := I on an (n_v x ncols) column-major block (rows >= ncols zeroed).
 int svdj_set_identity(int dtype, void* V, int n_v, int ldv, int ncols, int col_offset, void* stream);

@@ -32,6 +32,27 @@ class SVDResult:
         return iter((self.U, self.S, self.V))
 
 
+@dataclass
+class BatchedSVDResult:
+    """Result of :func:`svd_batched` for an input (..., m, n), k = min(m, n):
+    U (..., m, k), S (..., k), V (..., n, k) -- V, not V^T, like
+    :class:`SVDResult` -- and per matrix ``sweeps`` (int32), ``converged``
+    (bool: sweeps < max_sweeps or last off <= tol) and ``off`` (the largest
+    convergence value of the matrix's last sweep)."""
+
+    U: torch.Tensor | None
+    S: torch.Tensor
+    V: torch.Tensor | None
+    sweeps: torch.Tensor
+    converged: torch.Tensor
+    off: torch.Tensor
+    seconds: float = 0.0
+    info: dict = field(default_factory=dict)
+
+    def __iter__(self):  # U, S, V = svd_batched(A)
+        return iter((self.U, self.S, self.V))
+
+
 class Solver:
     """Base class of the solver families (models)."""
 

@@ -585,7 +585,47 @@ def block_solve(At, Vt, D, m_pad, W, tol, max_inner, max_sweeps, mma="native",
     return len(hist), hist
 
 
+# --------------------------------------------------------------- batched path
+BATCHED_MAX_N = 64  # csrc/hip/batched.hip kBatchedMaxN
+
+
+def batched_lds_bytes(dtype: torch.dtype, m: int, n: int, want_v: bool = True) -> int:
+    """LDS bytes one workgroup of the batched kernel takes for an (m x n)
+    matrix, m >= n (csrc/hip/batched.hip batched_layout); 0: the shape is
+    outside the kernel's envelope (n > 64, or it does not fit in 160 KiB)."""
+    return int(hip_lib().svdj_batched_lds_bytes(dtype_code(dtype), int(m), int(n), int(want_v)))
+
+
+def batched_threads(n: int) -> int:
+    """Threads of the workgroup that solves a matrix of n columns (0: n
+    outside the kernel's 1..64)."""
+    return int(hip_lib().svdj_batched_threads(int(n)))
+
+
+def batched_svd(A: torch.Tensor, tol: float, tol_mode=0, max_sweeps: int = 60,
+                want_u: bool = True, want_v: bool = True):
+    """SVD of every matrix of the device tensor ``A`` (batch, m, n), m >= n,
+    in one launch on the current stream (csrc/hip/batched.hip).  ``A`` is read
+    in place through its strides.  Returns (U (batch, m, n) or None, S (batch,
+    n), V (batch, n, n) or None, sweeps int32 (batch,), off float32 (batch,))."""
+    if A.dim() != 3 or not A.is_cuda:
+        raise ValueError("batched_svd: a (batch, m, n) device tensor")
+    B, m, n = A.shape
+    dev, dt = A.device, A.dtype
+    U = torch.empty(B, m, n, dtype=dt, device=dev) if want_u else None
+    S = torch.empty(B, n, dtype=dt, device=dev)
+    V = torch.empty(B, n, n, dtype=dt, device=dev) if want_v else None
+    sweeps = torch.empty(B, dtype=torch.int32, device=dev)
+    off = torch.empty(B, dtype=torch.float32, device=dev)
+    hip_check(hip_lib().svdj_batched_svd(
+        dtype_code(dt), B, m, n, _ptr(A), A.stride(0), A.stride(1), A.stride(2), _ptr(U), _ptr(S),
+        _ptr(V), float(tol), tol_mode_code(tol_mode), int(max_sweeps), _ptr(sweeps), _ptr(off),
+        _stream(A)), "batched_svd")
+    return U, S, V, sweeps, off
+
+
 __all__ = [
+    "batched_lds_bytes", "batched_threads", "batched_svd", "BATCHED_MAX_N",
     "NativeError", "ROW_ALIGN", "SUPPORTED_BLOCK", "INNER_ORDERS", "step_modes", "dtype_code", "new_metric", "reset_metric", "set_norm_floor",
     "METRIC_WORDS", "read_stop", "metric_stop_values", "metric_work", "sweep_converged", "STOP_RULES",
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
