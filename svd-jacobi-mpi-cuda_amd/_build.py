@@ -123,7 +123,7 @@ def build_driver(force: bool = False, verbose: bool = False) -> Path:
     return DRIVER_BIN
 
 
-DIST_SRC = CSRC / "dist" / "svdj_dist.cpp"
+DIST_SRC = CSRC / "distributed" / "svdj_dist.cpp"
 DIST_LIB = LIBDIR / "libsvdj_dist.so"
 DIST_DRIVER_SRC = CSRC / "driver" / "svdj_dist_main.cpp"
 DIST_DRIVER_BIN = PKG / "bin" / "svdj_dist_main"

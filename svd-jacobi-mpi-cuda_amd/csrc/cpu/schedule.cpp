@@ -102,8 +102,9 @@ extern "C" int svdj_bipartite(int k, int32_t* out) {
 
 // Quad orders (csrc/hip/block.hip "quad step"; parallel/schedule.py twins):
 // two consecutive steps fuse over the four blocks (a, b, c, d) of a
-// super-block pair {a, b} x {c, d}: step s pairs (a, c), (b, d), step s+1
-// (a, d), (b, c), as pairs 2q, 2q+1 of quad q.
+// super-block pair {a, b} x {c, d}: step s (SVDJ_STEP_QUAD, svdj_hip.h) pairs
+// (a, c), (b, d), step s+1 (SVDJ_STEP_QUAD_SECOND) (a, d), (b, c), as pairs
+// 2q, 2q+1 of quad q.
 extern "C" int svdj_quad_round_robin(int nb, int32_t* out) {
   if (nb < 4 || nb % 4 || out == nullptr) return -1;
   const int K = nb / 2;  // super-blocks (2i, 2i+1)

@@ -574,13 +574,13 @@ void template_hosts(svdj_dist_handle_t* h, int cross_mode, std::vector<int32_t>&
   const int k = h->k, hk = h->hk;
   std::vector<int32_t> rr((size_t)(k - 1) * (k / 2) * 2);
   std::vector<int32_t> rr_modes(k - 1, cross_mode);
-  if (h->quad) {  // quad order (block.hip "quad step"): modes 4 / 5 in pairs
+  if (h->quad) {  // quad order (block.hip "quad step"): quad steps and their seconds
     svdj_quad_round_robin(k, rr.data());
-    for (int s = 1; s < k - 1; ++s) rr_modes[s] = (s & 1) ? 4 : 5;
+    for (int s = 1; s < k - 1; ++s) rr_modes[s] = (s & 1) ? SVDJ_STEP_QUAD : SVDJ_STEP_QUAD_SECOND;
   } else {
     svdj_round_robin(k, rr.data());
   }
-  rr_modes[0] = 1;  // the first step of a sweep re-measures the diagonal (full Gram)
+  rr_modes[0] = SVDJ_STEP_FULL;  // the first step of a sweep re-measures the diagonal (full Gram)
   for (int s = 0; s < 2; ++s) {
     Template& t = h->rr[s];
     t.host = rr;
@@ -604,8 +604,8 @@ void template_hosts(svdj_dist_handle_t* h, int cross_mode, std::vector<int32_t>&
             ys[a] = stay * k + sh * hk + a;
           }
           svdj_quad_bipartite(hk, xs.data(), ys.data(), t.host.data());
-          t.modes.assign(hk, 4);
-          for (int s = 1; s < hk; s += 2) t.modes[s] = 5;
+          t.modes.assign(hk, SVDJ_STEP_QUAD);
+          for (int s = 1; s < hk; s += 2) t.modes[s] = SVDJ_STEP_QUAD_SECOND;
         } else {
           for (int q = 0; q < hk; ++q)
             for (int a = 0; a < hk; ++a) {
@@ -686,7 +686,7 @@ int build_templates(svdj_dist_handle_t* h, int cross_mode) {
 
 extern "C" int svdj_dist_issue_rules(int world, int dtype, int W, int mma, int k, int m_pad,
                                      int quad_mode, int* quad, int* merged) {
-  const bool quad_ok = dtype == 0 && W == 64 && (mma == 1 || mma == 2) && k % 4 == 0;
+  const bool quad_ok = dtype == 0 && W == 64 && svdj_mma_parts(mma) && k % 4 == 0;
   if (quad_mode < 0 || quad_mode > 2) return fail(-2, "quad %d (0 auto, 1 on, 2 off)", quad_mode);
   if (quad_mode == 1 && !quad_ok)
     return fail(-2, "quad steps need fp32, W = 64, a split-bf16 apply and k %% 4 == 0");
@@ -932,8 +932,9 @@ extern "C" int svdj_dist_handle_create(const svdj_dist_problem* p, void** out) {
   auto guard = [&](int r) {
     if (r < 0 && !rc) rc = r;
   };
-  // 3 = auto: by the pairs of a cross step (half super-blocks)
-  const int io = p->inner_order == 3 ? svdj_choose_inner_order(p->dtype, W, h->hk) : p->inner_order;
+  // auto: by the pairs of a cross step (half super-blocks)
+  const int io = p->inner_order == SVDJ_INNER_AUTO ? svdj_choose_inner_order(p->dtype, W, h->hk)
+                                                   : p->inner_order;
   h->io = io;
   // quad steps from 32 pairs per chain step on any number of GPUs, merged
   // issue on one GPU from 64 pairs (32 with quad steps) -- the Python
@@ -944,7 +945,7 @@ extern "C" int svdj_dist_handle_create(const svdj_dist_problem* p, void** out) {
   if (dr < 0) rc = dr;
   h->quad = quad != 0;
   h->merged = merged != 0;
-  if (!rc) guard(build_templates(h, io == 2 ? 3 : (io ? 2 : 0)));
+  if (!rc) guard(build_templates(h, svdj_cross_step_mode(io)));
   h->wsb = svdj_block_workspace_bytes(p->dtype, W, h->merged ? h->k : h->k / 2, p->m_pad,
                                       h->quad ? 1 : 0);
   for (int c = 0; c < 2 && !rc; ++c)
@@ -1123,7 +1124,7 @@ extern "C" int svdj_dist_solve(svdj_dist_problem* p, void* sigma) {
   std::vector<std::pair<double, double>> busy, waits;
   double comm_ms = 0, sweep_base_ms = 0;
   long long n_exch = 0, n_bytes = 0;
-  int mma_sweep = p->mma;  // the apply's mode, | 256 for a 2-part quad Gram (below)
+  int mma_sweep = p->mma;  // the apply's mode, | SVDJ_STEPS_GRAM2 for a 2-part quad Gram (below)
   // One sweep: every dependency is an event; the host never waits.
   auto sweep = [&]() -> int {
     std::vector<hipEvent_t> last[4];   // task events on each half since its last exchange
@@ -1216,7 +1217,7 @@ extern "C" int svdj_dist_solve(svdj_dist_problem* p, void* sigma) {
         SVDJC(svdj_block_steps(h->dtype, W, h->m_pad, p->At, h->m_pad, p->Vt, h->n_v, h->n_v, p->D,
                                dev_pairs(z), z.t->npairs, z.t->steps, z.t->modes.data(), p->tol,
                                p->tol_mode, 1, h->ws[cz], h->wsb, h->metric,
-                               mma_sweep | (h->quad ? 512 : 0), st[cz]));  // bit 9: chains share the GPU
+                               mma_sweep | (h->quad ? SVDJ_STEPS_SHARED_GPU : 0), st[cz]));
       }
       for (int q = 0; q < n_t; ++q) {
         const Item& x = items[idx[q]];
@@ -1270,13 +1271,14 @@ extern "C" int svdj_dist_solve(svdj_dist_problem* p, void* sigma) {
   p->calib_spread_ms = h->calib_ms[1];
   const auto t_solve = std::chrono::steady_clock::now();
   // Quad Gram precision per sweep (parallel/distributed.py, the same rule):
-  // 2 bf16 parts (svdj_block_steps' mma bit 8) while the previous sweep
+  // 2 bf16 parts (SVDJ_STEPS_GRAM2) while the previous sweep
   // rotated every pair; SVDJ_DEBUG gram2=0/1 forces it off / on (A/B).
   const long long nbt = 2LL * P * h->k, all_pairs = nbt * (nbt - 1) / 2;
   const int gram2 = svdj_debug_knob("gram2", -1);
   bool prev_all = true;
   for (int sw = 0; sw < p->max_sweeps && !rc; ++sw) {
-    mma_sweep = p->mma | ((h->quad && (gram2 < 0 ? prev_all : gram2 == 1)) ? 256 : 0);
+    mma_sweep =
+        p->mma | ((h->quad && (gram2 < 0 ? prev_all : gram2 == 1)) ? SVDJ_STEPS_GRAM2 : 0);
     if ((rc = sweep())) break;
     // ---- stop test (svdj_stop.h): global max convergence value and largest
     // applied |sin| (positive floats order as uint32), total rotated pairs

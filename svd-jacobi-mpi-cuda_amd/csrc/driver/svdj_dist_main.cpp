@@ -56,7 +56,7 @@
 namespace {
 
 struct Opts {
-  int n = 0, m = 0, np = 0, W = 0, max_sweeps = 60, mma = 0, warmup = 0, inner = 3;  // auto
+  int n = 0, m = 0, np = 0, W = 0, max_sweeps = 60, mma = 0, warmup = 0, inner = SVDJ_INNER_AUTO;
   int exchange = 0;  // auto
   int stop_rule = 1;  // second_order (svdj_stop.h)
   int quad = 0;       // auto
@@ -387,7 +387,10 @@ int main(int argc, char** argv) {
       o.exchange = v == "spread" ? 2 : (v == "direct" ? 1 : 0);
     } else if (a == "--inner") {
       const std::string v = next();
-      o.inner = v == "auto" ? 3 : (v == "cross" ? 2 : (v == "bipartite" ? 1 : 0));
+      o.inner = v == "auto"        ? SVDJ_INNER_AUTO
+                : v == "cross"     ? SVDJ_INNER_CROSS
+                : v == "bipartite" ? SVDJ_INNER_BIPARTITE
+                                   : SVDJ_INNER_CYCLIC;
     }
     else if (a == "--id-file") o.id_file = next();
     else if (a == "--comm-timing") o.comm_timing = true;
@@ -419,7 +422,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   // -1 = auto: svdj_choose_mma once the block width is known (run_rank)
-  if (o.f32) o.mma = mma == "auto" ? -1 : (mma == "bf16x6" ? 1 : (mma == "bf16x3" ? 2 : 0));
+  if (o.f32)
+    o.mma = mma == "auto"     ? -1
+            : mma == "bf16x6" ? SVDJ_MMA_BF16X6
+            : mma == "bf16x3" ? SVDJ_MMA_BF16X3
+                              : SVDJ_MMA_NATIVE;
 
   const char* env_rank = std::getenv("RANK");
   const char* env_world = std::getenv("WORLD_SIZE");

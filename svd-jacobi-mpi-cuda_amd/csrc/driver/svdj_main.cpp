@@ -208,7 +208,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "usage: %s N [--m M] [--input triu|dense] [--dtype f32|f64] ...\n", argv[0]);
     return 1;
   }
-  int n = std::atoi(argv[1]), m = n, W = 0, max_sweeps = 60, inner_order = 3;  // auto
+  int n = std::atoi(argv[1]), m = n, W = 0, max_sweeps = 60, inner_order = SVDJ_INNER_AUTO;
   unsigned seed = 1000000;
   double tol = -1;
   bool verify = false;
@@ -229,7 +229,10 @@ int main(int argc, char** argv) {
     else if (a == "--mma") mma = next();
     else if (a == "--inner") {
       const std::string v = next();
-      inner_order = v == "auto" ? 3 : (v == "cross" ? 2 : (v == "bipartite" ? 1 : 0));
+      inner_order = v == "auto"        ? SVDJ_INNER_AUTO
+                    : v == "cross"     ? SVDJ_INNER_CROSS
+                    : v == "bipartite" ? SVDJ_INNER_BIPARTITE
+                                       : SVDJ_INNER_CYCLIC;
     }
     else if (a == "--verify") verify = true;
     else if (a == "--report-dir") report_dir = next();
@@ -249,7 +252,9 @@ int main(int argc, char** argv) {
   if (W == 0)  // models/block.py choose_block
     W = dtype == "f32" ? (n >= 1024 ? 64 : 32) : ((m >= 6144 && n >= 2048) ? 64 : 32);
   const int mma_code = mma == "auto" ? svdj_choose_mma(dtype == "f32" ? 0 : 1, W)
-                                     : (mma == "bf16x6" ? 1 : (mma == "bf16x3" ? 2 : 0));
+                         : mma == "bf16x6" ? SVDJ_MMA_BF16X6
+                         : mma == "bf16x3" ? SVDJ_MMA_BF16X3
+                                           : SVDJ_MMA_NATIVE;
   if (engine != "pipeline" && engine != "steps") {
     std::fprintf(stderr, "--engine pipeline|steps\n");
     return 1;

@@ -40,20 +40,22 @@
 using namespace svdj;
 
 // Cross-step EVD ordering for a step of `pairs` pairs of W-wide blocks
-// (models/block.py choose_inner_order, measurements there): 2 = cross-only
+// (models/block.py choose_inner_order, measurements there): cross-only
 // (low-latency EVD + row-parallel Q build) for fp32 W = 64 and for fp64
-// W = 64 with more than 16 pairs, else 1 = bipartite.  The inner_order codes
-// of svdj_block_solve / svdj_dist_problem.
+// W = 64 with more than 16 pairs, else bipartite.  The inner_order codes
+// (SVDJ_INNER_*) of svdj_block_solve / svdj_dist_problem.
 extern "C" int svdj_choose_inner_order(int dtype, int W, int pairs) {
-  if (W != 64) return 1;
-  return (dtype == 0 || pairs > 16) ? 2 : 1;
+  if (W != 64) return SVDJ_INNER_BIPARTITE;
+  return (dtype == 0 || pairs > 16) ? SVDJ_INNER_CROSS : SVDJ_INNER_BIPARTITE;
 }
 
 // Default matrix-core mode ("auto") for data type `dtype` (0 fp32, 1 fp64)
 // and block width W (models/block.py choose_mma): the split-bf16 apply for
 // fp32 W = 64; W = 32 steps stay on f32 MFMA (4096^2 P=8
 // rank plan, W = 32: 8.55 vs 9.61 ms per sweep with the split).
-extern "C" int svdj_choose_mma(int dtype, int W) { return (dtype == 0 && W == 64) ? 1 : 0; }
+extern "C" int svdj_choose_mma(int dtype, int W) {
+  return (dtype == 0 && W == 64) ? SVDJ_MMA_BF16X6 : SVDJ_MMA_NATIVE;
+}
 
 extern "C" size_t svdj_block_workspace_bytes(int dtype, int W, int P, int m_pad, int quad) {
   return dtype == 1 ? solve_ws_bytes<double>(W, P, m_pad, quad != 0)
@@ -76,33 +78,13 @@ static int check_dims(int m_pad, int lda, const void* V, int n_v, int ldv, int m
   return 0;
 }
 
-template <typename T, int W>
-static int steps_dispatch(int m_pad, void* A, int lda, void* V, int n_v, int ldv, void* D,
-                          const int32_t* pairs, int P, int steps, const int32_t* modes,
-                          double tol, int absmode, int max_inner, void* ws, size_t ws_bytes,
-                          uint32_t* metric, int mma, void* stream) {
-  Chain<T> c;
-  const int gram2 = (mma >> 8) & 1;  // svdj_block_steps' mma bit 8
-  const int shared = (mma >> 9) & 1;  // bit 9
-  mma &= 0xff;
-  int rc = chain_init<T, W>(c, m_pad, (T*)A, lda, (T*)V, n_v, ldv, (T*)D, pairs, P, steps, modes,
-                            ws, ws_bytes, mma, (hipStream_t)stream);
-  if (rc) return rc;
-  if (gram2) c.gram_np = 2;
-  c.shared = shared;
-  return block_steps_t<T, W>(c, tol, absmode, max_inner, metric, mma);
-}
-
 extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,
                                 int ldv, void* D, const int32_t* pairs, int P, int steps,
                                 const int32_t* modes, double tol, int tol_mode, int max_inner,
                                 void* ws, size_t ws_bytes, uint32_t* metric, int mma,
                                 void* stream) {
-  // mma bits 0-7: the apply's matrix-core mode; bit 8: quad Gram with 2 bf16
-  // parts (gram_quad_kernel<0, 2>) for sweeps far from convergence; bit 9:
-  // another chain runs concurrently on this GPU (quad apply on
-  // quad_ts_grid_shared workgroups)
-  int rc = check_dims(m_pad, lda, V, n_v, ldv, mma & 0xff);
+  // mma: the apply's matrix-core mode | SVDJ_STEPS_* (svdj_hip.h; chain_init)
+  int rc = check_dims(m_pad, lda, V, n_v, ldv, mma & SVDJ_MMA_MASK);
   if (rc) return rc;
   if (tol_mode != 0 && tol_mode != 1) {
     set_error("bad tol_mode %d (0 relative, 1 absolute)", tol_mode);
@@ -110,9 +92,13 @@ extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, v
   }
   if (P <= 0 || steps < 0) return 0;
   return dispatch_tw(dtype, W, [&](auto t, auto w) {
-    return steps_dispatch<decltype(t), decltype(w)::value>(
-        m_pad, A, lda, V, n_v, ldv, D, pairs, P, steps, modes, tol, tol_mode, max_inner, ws,
-        ws_bytes, metric, mma, stream);
+    using T = decltype(t);
+    constexpr int W_ = decltype(w)::value;
+    Chain<T> c;
+    const int err = chain_init<T, W_>(c, m_pad, (T*)A, lda, (T*)V, n_v, ldv, (T*)D, pairs, P,
+                                      steps, modes, tol, tol_mode, max_inner, ws, ws_bytes, metric,
+                                      mma, (hipStream_t)stream);
+    return err ? err : block_steps_t<T, W_>(c);
   });
 }
 
@@ -142,13 +128,13 @@ extern "C" int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, v
       o[2 * k + 1] = a < b ? b : a;
     }
   }
-  if (inner_order == 3) inner_order = svdj_choose_inner_order(dtype, W, P);  // auto
-  if (inner_order < 0 || inner_order > 2) {
+  if (inner_order == SVDJ_INNER_AUTO) inner_order = svdj_choose_inner_order(dtype, W, P);
+  if (inner_order < SVDJ_INNER_CYCLIC || inner_order > SVDJ_INNER_CROSS) {
     set_error("inner_order %d (0 cyclic, 1 bipartite, 2 cross, 3 auto)", inner_order);
     return -2;
   }
-  std::vector<int32_t> modes(steps, inner_order == 2 ? 3 : (inner_order ? 2 : 0));
-  modes[0] = 1;
+  std::vector<int32_t> modes(steps, svdj_cross_step_mode(inner_order));
+  modes[0] = SVDJ_STEP_FULL;
   hipStream_t st = (hipStream_t)stream;
   int32_t* dpairs = nullptr;
   SVDJ_HIP_CHECK(hipMallocAsync((void**)&dpairs, h.size() * sizeof(int32_t), st));
@@ -200,13 +186,13 @@ extern "C" int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_p
     set_error("svdj_gram_cross: lda %d must be a multiple of 4", lda);
     return -2;
   }
-  Chain<float> c{};  // the fields launch_gram reads
+  Chain<float> c{};  // the fields launch_gram reads (no modes: a cross step)
   c.A = const_cast<float*>((const float*)A);  // only read by the Gram
   c.lda = lda; c.m_pad = m_pad; c.pairs = pairs; c.P = P; c.st = (hipStream_t)stream;
   c.g.grows = rows_per_chunk;
   c.g.gchunks = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
   c.slabs = (float*)slabs;
-  return W == 64 ? launch_gram<float, 64>(c, 0, 0) : launch_gram<float, 32>(c, 0, 0);
+  return W == 64 ? launch_gram<float, 64>(c, 0) : launch_gram<float, 32>(c, 0);
 }
 
 // The six cross Grams of a quad step (fp32, W = 64) alone (tests / kernel
@@ -265,10 +251,10 @@ extern "C" int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, in
 
 // The middle of a single step alone (tests): launch_evd -- what a step of
 // svdj_block_steps runs after its Gram -- on slabs given by the caller.
-//   slabs   device, data type: P x nchunk x W x W (mode 1: 2W x 2W), the
-//           layout the Gram kernels write; copied into the workspace's slab area
+//   slabs   device, data type: P x nchunk x W x W (SVDJ_STEP_FULL: 2W x 2W),
+//           the layout the Gram kernels write; copied into the workspace's slab area
 //   D       squared column norms by block (updated in place), pairs device
-//           int32 [P][2], mode 0 - 3 as launch_gram_evd
+//           int32 [P][2], mode SVDJ_STEP_CROSS to SVDJ_STEP_CROSS_ONLY
 //   Q       out, P x 2W x 2W (data type; a skipped pair's may stay unwritten)
 //   skip    out, int32 [P]
 //   ws      svdj_evd_alone_workspace_bytes: the slab area of a step with
@@ -286,15 +272,18 @@ extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int
   return dispatch_tw(dtype, W, [&](auto t, auto w) {
     using T = decltype(t);
     constexpr int W_ = decltype(w)::value;
-    if (mode < 0 || mode > 3 || P < 1 || nchunk < 1 || max_inner < 0 ||
+    if (mode < 0 || mode > SVDJ_STEP_CROSS_ONLY || P < 1 || nchunk < 1 || max_inner < 0 ||
         (tol_mode != 0 && tol_mode != 1) || !slabs || !D || !pairs || !Q || !skip || !ws ||
         !metric) {
       set_error("svdj_evd_alone: bad mode/P/nchunk/max_inner/tol_mode %d/%d/%d/%d/%d or a null "
                 "pointer", mode, P, nchunk, max_inner, tol_mode);
       return -2;
     }
+    const int32_t modes[1] = {mode};  // c.modes: must outlive the launch_evd call below
     Chain<T> c{};  // the fields launch_evd reads
-    c.P = P; c.steps = 1; c.D = (T*)D; c.pairs = pairs; c.st = (hipStream_t)stream;
+    c.P = P; c.steps = 1; c.D = (T*)D; c.pairs = pairs; c.modes = modes;
+    c.st = (hipStream_t)stream;
+    c.tol = tol; c.tol_mode = tol_mode; c.max_inner = max_inner; c.metric = metric;
     c.g.gchunks = nchunk;
     c.Qb[0] = (T*)Q;
     c.skipb[0] = skip;
@@ -303,9 +292,10 @@ extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int
       set_error("svdj_evd_alone: workspace too small: %zu < %zu", ws_bytes, need);
       return -2;
     }
-    const size_t in_bytes = (size_t)P * nchunk * (mode == 1 ? 4 : 1) * W_ * W_ * sizeof(T);
+    const int full = mode == SVDJ_STEP_FULL;
+    const size_t in_bytes = (size_t)P * nchunk * (full ? 4 : 1) * W_ * W_ * sizeof(T);
     SVDJ_HIP_CHECK(hipMemcpyAsync(c.slabs, slabs, in_bytes, hipMemcpyDeviceToDevice, c.st));
-    return launch_evd<T, W_>(c, 0, mode, tol, tol_mode, max_inner, metric);
+    return launch_evd<T, W_>(c, 0);
   });
 }
 
@@ -313,9 +303,9 @@ extern "C" int svdj_evd_alone(int dtype, int W, int mode, const void* slabs, int
 // what a quad step of svdj_block_steps runs after its Gram -- on slabs given
 // by the caller, read in place.
 //   slabs   device fp32, 3P x nchunk x 64 x 64 in svdj_gram_quad's order
-//   pairs   device int32 [2][P][2]: the step's pairs in quad order ((a,c),
-//           (b,d) per quad: mode 4), then those of the next ((a,d), (b,c): mode 5)
-//   np      parts of the split T: 3 / 2 (mma 1 / 2 of svdj_block_steps)
+//   pairs   device int32 [2][P][2]: the SVDJ_STEP_QUAD step's pairs in quad order
+//           ((a,c), (b,d) per quad), then those of its second step ((a,d), (b,c))
+//   np      parts of the split T: svdj_mma_parts of svdj_block_steps' mma
 //   T1      out, fp64 P x 128 x 128; upd out, fp32 P x 64 x 64; Ts out, bf16
 //           (P / 2) x 256 x 256 x np (svdj_apply_quad's layout); skip1, skip2
 //           out, int32 [P] each
@@ -338,10 +328,11 @@ extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int
               P, nchunk, max_inner, tol_mode, np);
     return -2;
   }
-  static const int32_t modes[2] = {4, 5};
+  static const int32_t modes[2] = {SVDJ_STEP_QUAD, SVDJ_STEP_QUAD_SECOND};
   Chain<float> c{};  // the fields launch_quad_chain reads
   c.P = P; c.steps = 2; c.D = (float*)D; c.pairs = pairs; c.modes = modes;
-  c.st = (hipStream_t)stream;
+  c.st = (hipStream_t)stream; c.mma = np == 2 ? SVDJ_MMA_BF16X3 : SVDJ_MMA_BF16X6;
+  c.tol = tol; c.tol_mode = tol_mode; c.max_inner = max_inner; c.metric = metric;
   const size_t need = quad_chain_layout(c, ws);
   if (ws_bytes < need) {
     set_error("svdj_quad_chain: workspace too small: %zu < %zu", ws_bytes, need);
@@ -354,8 +345,8 @@ extern "C" int svdj_quad_chain(const void* slabs, int nchunk, void* D, const int
   c.Ts[0] = (bf16x8*)Ts;
   c.skip1[0] = skip1;
   c.skip2[0] = skip2;
-  if (!quad_step_ok(c.P, 0, c.steps, c.modes)) return -2;
-  return launch_quad_chain<float, 64>(c, 0, tol, tol_mode, max_inner, metric, np == 2 ? 2 : 1);
+  if (!quad_step_ok(c, 0)) return -2;
+  return launch_quad_chain<float, 64>(c, 0);
 }
 
 // Test/diagnostic hook: X <- X Q for ONE column-block pair (blocks 0 and 1 of
@@ -376,19 +367,21 @@ extern "C" int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld
   SVDJ_HIP_CHECK(hipMemcpyAsync(dbuf, hpair, 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SVDJ_HIP_CHECK(hipMemcpyAsync(dbuf + 2, hskip, sizeof(int32_t), hipMemcpyHostToDevice, st));
   int rc = -3;
-  if (mma < 0 || mma > 2 || (dtype == 1 && mma != 0))
+  if (mma < 0 || mma > 2 || (dtype == 1 && mma != SVDJ_MMA_NATIVE))
     set_error("svdj_apply_q: unsupported dtype=%d W=%d mma=%d", dtype, W, mma);
   else
     rc = dispatch_tw(dtype, W, [&](auto t, auto w) {
       using T = decltype(t);
-      // the fields launch_apply reads (no modes: mode 0; no V: A's row chunks only)
+      // the fields launch_apply reads (no modes: a cross step; no V: A's row
+      // chunks only; no metric: only a quad step's apply counts its work)
       Chain<T> c{};
       c.A = (T*)X; c.lda = ld; c.m_pad = rows; c.pairs = dbuf; c.P = 1; c.st = st;
+      c.mma = mma;
       c.g.rows_a = 512;
       c.g.a_chunks = (rows + c.g.rows_a - 1) / c.g.rows_a;
       c.Qb[0] = const_cast<T*>((const T*)Q);  // only read by the apply
       c.skipb[0] = dbuf + 2;
-      return launch_apply<T, decltype(w)::value>(c, 0, mma, nullptr);
+      return launch_apply<T, decltype(w)::value>(c, 0);
     });
   (void)hipFreeAsync(dbuf, st);
   return rc;

@@ -1,7 +1,11 @@
 // Host side of the block Jacobi step (block.hip), part 2: the launchers.  A
-// chain's steps run gram(s) -> evd(s) -> apply(s) on its stream
-// (block_steps_t); the launch_* routines are also what the C entry points of
-// block.hip that run one stage alone call.
+// chain's steps run gram(s) -> evd(s) -> apply(s) on its stream (block_steps_t).
+// Every launch_* routine takes the chain and a step index and reads the rest --
+// buffers, the step's mode (SVDJ_STEP_*, svdj_hip.h), tolerance, inner sweeps,
+// metric, matrix-core mode -- from the Chain record (block_layout.hpp), which
+// chain_init fills for a solve and the C entry points of block.hip that run one
+// stage alone fill for their launcher.  Only launch_quad_apply takes explicit
+// parameters: its hook passes values a solve never uses.
 #pragma once
 #include "block_apply.hpp"
 #include "block_evd.hpp"
@@ -16,10 +20,13 @@
 
 namespace svdj {
 
+// flags: svdj_block_steps' mma word (matrix-core mode | SVDJ_STEPS_*).
 template <typename T, int W>
 static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int ldv, T* D,
-                      const int32_t* pairs, int P, int steps, const int32_t* modes, void* ws,
-                      size_t ws_bytes, int mma, hipStream_t st) {
+                      const int32_t* pairs, int P, int steps, const int32_t* modes, double tol,
+                      int tol_mode, int max_inner, void* ws, size_t ws_bytes, uint32_t* metric,
+                      int flags, hipStream_t st) {
+  const int mma = flags & SVDJ_MMA_MASK;
   const bool quad = has_quad_steps(modes, steps);
   if (quad && !has_quad(sizeof(T), W)) {
     set_error("quad steps need fp32 data and W = 64");
@@ -30,7 +37,7 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
     set_error("workspace too small: %zu < %zu", ws_bytes, need);
     return -4;
   }
-  if (mma != 0 && sizeof(T) != 4) {
+  if (mma != SVDJ_MMA_NATIVE && sizeof(T) != 4) {
     set_error("split-bf16 matrix-core modes need fp32 data");
     return -3;
   }
@@ -40,8 +47,10 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
   }
   c = Chain<T>{};
   c.m_pad = m_pad; c.lda = lda; c.n_v = n_v; c.ldv = ldv; c.P = P; c.steps = steps;
-  c.gram_np = 3;
   c.A = A; c.V = V; c.D = D; c.pairs = pairs; c.modes = modes; c.st = st;
+  c.tol = tol; c.tol_mode = tol_mode; c.max_inner = max_inner; c.metric = metric; c.mma = mma;
+  c.gram_np = (flags & SVDJ_STEPS_GRAM2) ? 2 : 3;
+  c.shared = (flags & SVDJ_STEPS_SHARED_GPU) != 0;
   c.g = make_geometry(W, P, m_pad, V ? n_v : 0, mma);
   solve_layout(c, ws, W, quad);
   return 0;
@@ -49,9 +58,10 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
 
 // Quad step s (steps s, s+1 fused; see "quad step"): gram (launch_quad_gram),
 // then evd 1, T1, update, evd 2, T (launch_quad_chain) on the chain's stream.
-static bool quad_step_ok(int P, int s, int steps, const int32_t* modes) {
-  if (P % 2 || s + 1 >= steps || !modes || modes[s + 1] != 5) {
-    set_error("quad step %d: needs an even pair count (%d) and a following mode-5 step", s, P);
+template <typename T>
+static bool quad_step_ok(const Chain<T>& c, int s) {
+  if (c.P % 2 || s + 1 >= c.steps || step_mode(c.modes, s + 1) != SVDJ_STEP_QUAD_SECOND) {
+    set_error("quad step %d: needs an even pair count (%d) and a following mode-5 step", s, c.P);
     return false;
   }
   return true;
@@ -88,8 +98,7 @@ static int launch_quad_gram(const Chain<T>& c, int s) {
 // T1, update, evd 2, T.  (Also what svdj_quad_chain runs, on slabs given by
 // its caller.)
 template <typename T, int W>
-static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
-                             uint32_t* metric, int mma) {
+static int launch_quad_chain(const Chain<T>& c, int s) {
   if constexpr (sizeof(T) == 4 && W == 64) {
     const int b = s & 1;
     const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
@@ -104,8 +113,8 @@ static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, 
       SVDJ_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL((evd_cross_kernel<float, 64>), dim3(c.P), dim3(cross_threads<64>()), 0, c.st,
-                       pr, gs, gn, c.D, c.rec, c.nsteps, c.skip1[b], (float)tol,
-                       absmode, max_inner, metric);
+                       pr, gs, gn, c.D, c.rec, c.nsteps, c.skip1[b], (float)c.tol,
+                       c.tol_mode, c.max_inner, c.metric);
     SVDJ_LAUNCH_CHECK();
     constexpr int R = 8;
     // 1024 threads: one workgroup per pair (phase 1) / two (phase 2), so each
@@ -137,11 +146,11 @@ static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, 
                          gs + (size_t)c.P * gn * 64 * 64, gn, c.T1, c.upd);
     SVDJ_LAUNCH_CHECK();
     hipLaunchKernelGGL((evd_cross_kernel<float, 64>), dim3(c.P), dim3(cross_threads<64>()), 0, c.st,
-                       pr1, c.upd, 1, c.D, c.rec, c.nsteps, c.skip2[b], (float)tol, absmode,
-                       max_inner, metric);
+                       pr1, c.upd, 1, c.D, c.rec, c.nsteps, c.skip2[b], (float)c.tol, c.tol_mode,
+                       c.max_inner, c.metric);
     SVDJ_LAUNCH_CHECK();
     // the split T is written directly (no tsplit pass)
-    with_parts(mma == 2 ? 2 : 3, [&](auto np) {
+    with_parts(svdj_mma_parts(c.mma), [&](auto np) {
       constexpr int NP = decltype(np)::value;
       if (lat)
         hipLaunchKernelGGL((qbuild_quad_kernel<2, 2, QBT, NP>), dim3(c.P, 256 / (2 * QBW)),
@@ -153,18 +162,17 @@ static int launch_quad_chain(const Chain<T>& c, int s, double tol, int absmode, 
     SVDJ_LAUNCH_CHECK();
     return 0;
   } else {
-    (void)c; (void)s; (void)tol; (void)absmode; (void)max_inner; (void)metric; (void)mma;
+    (void)c; (void)s;
     set_error("quad steps need fp32 data and W = 64");
     return -3;
   }
 }
 
 template <typename T, int W>
-static int launch_quad_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
-                                uint32_t* metric, int mma) {
-  if (sizeof(T) == 4 && W == 64 && !quad_step_ok(c.P, s, c.steps, c.modes)) return -2;
+static int launch_quad_gram_evd(const Chain<T>& c, int s) {
+  if (sizeof(T) == 4 && W == 64 && !quad_step_ok(c, s)) return -2;
   const int rc = launch_quad_gram<T, W>(c, s);
-  return rc ? rc : launch_quad_chain<T, W>(c, s, tol, absmode, max_inner, metric, mma);
+  return rc ? rc : launch_quad_chain<T, W>(c, s);
 }
 
 // Gram + EVD of step s (Q and the skip flags are double-buffered so evd(s+1)
@@ -179,11 +187,11 @@ static int stream_order() {
   return v;
 }
 
-// The Gram of step s (mode 0 - 3) into c.slabs (c.g.gchunks row chunks).
+// The Gram of step s (cross or full) into c.slabs (c.g.gchunks row chunks).
 template <typename T, int W>
-static int launch_gram(const Chain<T>& c, int s, int mode) {
+static int launch_gram(const Chain<T>& c, int s) {
   const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
-  const int full = mode == 1;
+  const int full = step_mode(c.modes, s) == SVDJ_STEP_FULL;
   constexpr int XS = gram_xsplit<T, W>();
   if (full) {
     if constexpr (XS > 1)  // see GRAM_SPLIT
@@ -204,16 +212,16 @@ static int launch_gram(const Chain<T>& c, int s, int mode) {
   return 0;
 }
 
-// Everything of step s (mode 0 - 3) after its Gram, from the slabs in
-// c.slabs: the EVD and, for mode 3, the chunk pre-sum and the Q build.  (Also
-// what svdj_evd_alone runs, on slabs given by its caller.)
+// Everything of step s (cross or full) after its Gram, from the slabs in
+// c.slabs: the EVD and, for SVDJ_STEP_CROSS_ONLY, the chunk pre-sum and the Q
+// build.  (Also what svdj_evd_alone runs, on slabs given by its caller.)
 template <typename T, int W>
-static int launch_evd(const Chain<T>& c, int s, int mode, double tol, int absmode, int max_inner,
-                      uint32_t* metric) {
+static int launch_evd(const Chain<T>& c, int s) {
   const int b = s & 1;
   const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
-  const int full = mode == 1;
-  if (mode == 3) {
+  const int mode = step_mode(c.modes, s);
+  const int full = mode == SVDJ_STEP_FULL;
+  if (mode == SVDJ_STEP_CROSS_ONLY) {
     // many row chunks (few pairs per step: the 8-GPU plans read 32): sum them
     // once, wide, instead of on the EVD's critical path (one workgroup per
     // pair reading every chunk); bitwise the same sums (slab_reduce_kernel)
@@ -230,7 +238,8 @@ static int launch_evd(const Chain<T>& c, int s, int mode, double tol, int absmod
       }
     }
     hipLaunchKernelGGL((evd_cross_kernel<T, W>), dim3(c.P), dim3(cross_threads<W>()), 0, c.st, pr,
-                       gs, gn, c.D, c.rec, c.nsteps, c.skipb[b], (T)tol, absmode, max_inner, metric);
+                       gs, gn, c.D, c.rec, c.nsteps, c.skipb[b], (T)c.tol, c.tol_mode, c.max_inner,
+                       c.metric);
     SVDJ_LAUNCH_CHECK();
     constexpr int RL = W == 64 ? 16 : 8;  // one workgroup per pair
     // 16 rows per lane from 64 pairs per step; at 32 pairs 4 rows per lane is
@@ -248,28 +257,25 @@ static int launch_evd(const Chain<T>& c, int s, int mode, double tol, int absmod
     else
       hipLaunchKernelGGL((qbuild_kernel<T, W, 4>), dim3(c.P, qbuild_blocks<W, 4>()),
                          dim3(kQbThreads), 0, c.st, c.rec, c.nsteps, c.skipb[b], c.Qb[b]);
-  } else if (mode == 2)
+  } else if (mode == SVDJ_STEP_CROSS_BIP)
     hipLaunchKernelGGL((evd_kernel<T, W, EVD_BIP>), dim3(c.P), dim3(evd_threads(W)), 0, c.st, pr,
-                       0, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)tol, absmode,
-                       max_inner, metric);
+                       0, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol, c.tol_mode,
+                       c.max_inner, c.metric);
   else
     hipLaunchKernelGGL((evd_kernel<T, W, EVD_CYCLIC>), dim3(c.P), dim3(evd_threads(W)), 0, c.st,
-                       pr, full, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)tol, absmode,
-                       max_inner, metric);
+                       pr, full, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol,
+                       c.tol_mode, c.max_inner, c.metric);
   SVDJ_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T, int W>
-static int launch_gram_evd(const Chain<T>& c, int s, double tol, int absmode, int max_inner,
-                           uint32_t* metric, int mma) {
-  // 0 cross (cyclic EVD), 1 full Gram, 2 cross + bipartite EVD, 3 cross +
-  // cross-only bipartite EVD (evd_cross_kernel)
-  const int mode = c.modes ? c.modes[s] : 0;
-  if (mode == 5) return 0;  // second step of a quad: done by its first (mode 4)
-  if (mode == 4) return launch_quad_gram_evd<T, W>(c, s, tol, absmode, max_inner, metric, mma);
-  const int rc = launch_gram<T, W>(c, s, mode);
-  return rc ? rc : launch_evd<T, W>(c, s, mode, tol, absmode, max_inner, metric);
+static int launch_gram_evd(const Chain<T>& c, int s) {
+  const int mode = step_mode(c.modes, s);
+  if (mode == SVDJ_STEP_QUAD_SECOND) return 0;  // done by the quad's first step
+  if (mode == SVDJ_STEP_QUAD) return launch_quad_gram_evd<T, W>(c, s);
+  const int rc = launch_gram<T, W>(c, s);
+  return rc ? rc : launch_evd<T, W>(c, s);
 }
 
 // The apply of quad step s (T-stationary, persistent: apply_quad_ts_kernel<np>
@@ -294,16 +300,16 @@ static int launch_quad_apply(const Chain<float>& c, int s, int np, int grid, flo
 }
 
 template <typename T, int W>
-static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
+static int launch_apply(const Chain<T>& c, int s) {
   const int b = s & 1;
   const int32_t* pr = c.pairs + (size_t)s * c.P * 2;
   const int nv = c.V ? c.n_v : 0, ych = c.V ? c.g.v_chunks : 0;
-  const int mode = c.modes ? c.modes[s] : 0;
-  if (mode == 5) return 0;
-  if (mode == 4) {
+  const int mode = step_mode(c.modes, s), parts = svdj_mma_parts(c.mma);
+  if (mode == SVDJ_STEP_QUAD_SECOND) return 0;
+  if (mode == SVDJ_STEP_QUAD) {
     if constexpr (sizeof(T) == 4 && W == 64) {
-      if (mma != 1 && mma != 2) {
-        set_error("quad steps run the split-bf16 apply (mma 1 or 2), got %d", mma);
+      if (!parts) {
+        set_error("quad steps run the split-bf16 apply (mma 1 or 2), got %d", c.mma);
         return -3;
       }
       // cheap k halves: |T - I| <= 2^-7 (A/B only: SVDJ_DEBUG cheap_log2, svdj_debug.h)
@@ -312,8 +318,7 @@ static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
       static const int grid_knob = svdj_debug_knob("apply_grid", 0);
       const int grid =
           grid_knob > 0 ? grid_knob : c.shared ? quad_ts_grid_shared(c.P / 2) : kQuadTsGrid;
-      return launch_quad_apply(c, s, mma == 1 ? 3 : 2, grid, cheap_tol,
-                               metric ? metric + 6 : nullptr);
+      return launch_quad_apply(c, s, parts, grid, cheap_tol, c.metric ? c.metric + 6 : nullptr);
     } else {
       set_error("quad steps need fp32 data and W = 64");
       return -3;
@@ -321,8 +326,8 @@ static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
   }
   const dim3 grid(c.P, c.g.a_chunks + ych);
   if constexpr (sizeof(T) == 4) {
-    if (mma == 1 || mma == 2) {
-      with_parts(mma == 2 ? 2 : 3, [&](auto np) {
+    if (parts) {
+      with_parts(parts, [&](auto np) {
         hipLaunchKernelGGL((apply_split_kernel<W, decltype(np)::value>), grid, dim3(kApplyThreads),
                            0, c.st, c.A, c.lda, c.g.a_chunks, c.g.rows_a, c.m_pad, c.V, c.ldv,
                            c.g.rows_v, nv, pr, c.Qb[b], c.skipb[b], (stream_order() >> 1) & 1);
@@ -340,23 +345,22 @@ static int launch_apply(const Chain<T>& c, int s, int mma, uint32_t* metric) {
 
 // Step pipeline on the chain's stream: gram(s) -> evd(s) -> apply(s).
 //
-// mma: 0 = native matrix cores for the data type (f32 / f64 MFMA),
-//      1 = fp32 data on bf16 MFMA, 3-way split (fp32-level accuracy),
-//      2 = fp32 data on bf16 MFMA, 2-way split (~2^-17 accuracy, fast mode).
+// c.mma: SVDJ_MMA_NATIVE = native matrix cores for the data type (f32 / f64 MFMA),
+//        SVDJ_MMA_BF16X6 = fp32 data on bf16 MFMA, 3-way split (fp32-level accuracy),
+//        SVDJ_MMA_BF16X3 = fp32 data on bf16 MFMA, 2-way split (~2^-17, fast mode).
 // Both split modes run in delta form, Y = X + X (Q - I) (apply_split_kernel).
 // Measured on MI355X (bench.py accuracy block, profiles/r3_s3/bf16x6,
-// profiles/r4_accuracy): mode 1 matches the f32 MFMA path in U/V orthogonality
+// profiles/r4_accuracy): BF16X6 matches the f32 MFMA path in U/V orthogonality
 // and sigma error (16384^2: 2.43e-7 both), its residual is 1.37-1.55e-5 vs
 // 1.03-1.05e-5, and it is 12-23 % faster per sweep for W = 64, so it is the
 // fp32 default there (svdj_choose_mma).  Deferring V's rotation to a side
 // stream (it is not needed by the next Gram) was measured neutral on one
 // stream and 22 % slower with two chains (8192^2, round 4): not kept.
 template <typename T, int W>
-static int block_steps_t(const Chain<T>& c, double tol, int absmode, int max_inner,
-                         uint32_t* metric, int mma) {
+static int block_steps_t(const Chain<T>& c) {
   for (int s = 0; s < c.steps; ++s) {
-    int rc = launch_gram_evd<T, W>(c, s, tol, absmode, max_inner, metric, mma);
-    if (!rc) rc = launch_apply<T, W>(c, s, mma, metric);
+    int rc = launch_gram_evd<T, W>(c, s);
+    if (!rc) rc = launch_apply<T, W>(c, s);
     if (rc) return rc;
   }
   return 0;

@@ -5,6 +5,7 @@
 #pragma once
 #include "common.hpp"
 #include "svdj_debug.h"
+#include "svdj_hip.h"
 
 namespace svdj {
 
@@ -95,19 +96,28 @@ static Geometry make_geometry(int W, int P, int m_pad, int n_v, int mma = 0) {
 }
 
 static bool has_quad(int esize, int W) { return esize == 4 && W == 64; }
+// Mode (SVDJ_STEP_*, svdj_hip.h) of step s of a mode list; no list: all cross.
+static int step_mode(const int32_t* modes, int s) { return modes ? modes[s] : SVDJ_STEP_CROSS; }
 static bool has_quad_steps(const int32_t* modes, int steps) {
   for (int s = 0; modes && s < steps; ++s)
-    if (modes[s] == 4) return true;
+    if (modes[s] == SVDJ_STEP_QUAD) return true;
   return false;
 }
 
-// One chain of steps: resident buffers, its pair list and its workspace.
+// One chain of steps: resident buffers, its pair list, the parameters of its
+// steps and its workspace.
 template <typename T>
 struct Chain {
   int m_pad, lda, n_v, ldv, P, steps;
   T *A, *V, *D;
   const int32_t* pairs;
   const int32_t* modes;
+  double tol;  // the EVDs' rotation threshold, relative or (tol_mode 1) absolute
+  int tol_mode, max_inner;
+  uint32_t* metric;  // svdj_stop.h
+  int mma;  // the apply's matrix-core mode (SVDJ_MMA_*)
+  int gram_np;  // bf16 parts of the quad Gram (3; 2: SVDJ_STEPS_GRAM2)
+  int shared;  // another chain runs concurrently on this GPU (SVDJ_STEPS_SHARED_GPU)
   Geometry g;
   T* slabs;
   T* xsum;  // cross slabs summed over their row chunks, inside the slab area (launch_evd)
@@ -124,8 +134,6 @@ struct Chain {
   int32_t* skip1[2];
   int32_t* skip2[2];
   hipStream_t st;
-  int gram_np;  // bf16 parts of the quad Gram (3; 2 far from convergence)
-  int shared;  // another chain runs concurrently on this GPU (svdj_block_steps mma bit 9)
 };
 
 // Workspace areas in the order they are taken, each rounded up to 256 bytes.

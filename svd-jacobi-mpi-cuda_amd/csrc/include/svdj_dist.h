@@ -71,9 +71,9 @@ typedef struct {
   double tol;
   int tol_mode;               // 0 relative, 1 absolute
   int max_sweeps;
-  int mma;                    // matrix-core mode of the apply (svdj_block_steps)
-  int inner_order;            // EVD of the cross steps: 0 cyclic, 1 bipartite (mode 2),
-                              // 2 cross-only bipartite (mode 3), 3 auto
+  int mma;                    // matrix-core mode of the apply (SVDJ_MMA_*, svdj_hip.h)
+  int inner_order;            // EVD of the cross steps (SVDJ_INNER_*, svdj_hip.h):
+                              // 0 cyclic, 1 bipartite, 2 cross-only bipartite, 3 auto
                               // (svdj_choose_inner_order of the half super-block pairs)
   int exchange;               // half super-block transfer: 0 auto (from 4 ranks both are
                               // timed on the job's links when the handle is created and
@@ -155,7 +155,8 @@ int svdj_dist_issue_rules(int world, int dtype, int W, int mma, int k, int m_pad
 // One-GPU merged issue (host only, for tests): the pair lists of the three
 // merged task groups of a sweep with k blocks per super-block (rr0+rr1,
 // T00+T11, T01+T10; local block ids), concatenated step by step; modes[] the
-// step modes of each group in turn, meta[3][3] {offset, steps, pairs/step}.
+// step modes (SVDJ_STEP_*, svdj_hip.h; cross_mode: the cross steps') of each
+// group in turn, meta[3][3] {offset, steps, pairs/step}.
 // Returns the number of ints written to pairs, or <0.
 int svdj_dist_merged_lists(int k, int quad, int cross_mode, int32_t* pairs, int pcap,
                            int32_t* modes, int mcap, int32_t* meta);

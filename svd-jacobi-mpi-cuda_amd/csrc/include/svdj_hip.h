@@ -51,39 +51,85 @@ int svdj_scalar_solve(int dtype, int m_pad, void* A, int lda, void* V, int n_v,
 // Block path (one-sided block Jacobi, MFMA).  Columns are grouped in blocks
 // of W (32 or 64; fp64 supports 32).  One step processes P disjoint block
 // pairs (bi, bj):
-//   1. Gram (MFMA, split over rows):  mode 0 (cross) C = A_bi^T A_bj,
-//                                     mode 1 (full)  G = [A_bi A_bj]^T[..]
+//   1. Gram (MFMA, split over rows):  cross C = A_bi^T A_bj,
+//                                     full  G = [A_bi A_bj]^T[..]
 //   2. EVD of the 2W x 2W Gram (cyclic parallel Jacobi in LDS), in cross
 //      mode with the diagonal blocks taken from the tracked squared column
 //      norms D (blocks are kept internally orthogonal);  Q -> workspace.
 //   3. Apply (MFMA):  [A_bi A_bj] <- [A_bi A_bj] Q ,  [V_bi V_bj] <- .. Q
 // D (device, dtype, [ncols]) holds squared column norms; updated in place.
 //   pairs   device int32 [steps][P][2] block indices
-//   modes   host   int32 [steps] (0 cross / 1 full / 2 cross with the bipartite
-//           EVD ordering, W steps instead of 2W-1 / 3 cross with the
-//           cross-only bipartite EVD), NULL = all cross
+//   modes   host   int32 [steps] of SVDJ_STEP_* (below), NULL = all
+//           SVDJ_STEP_CROSS:
+//             CROSS       cross Gram, cyclic EVD (2W-1 EVD steps)
+//             FULL        full Gram, cyclic EVD
+//             CROSS_BIP   cross Gram, bipartite EVD ordering (W EVD steps)
+//             CROSS_ONLY  cross Gram, cross-only bipartite EVD + Q build
+//             QUAD        first step of a quad (fp32, W = 64, a split-bf16
+//                         mma): steps s and s+1 over the four blocks of every
+//                         two consecutive pairs, (a,c),(b,d) then (a,d),(b,c),
+//                         run fused -- six cross Grams, two cross EVDs, one
+//                         apply.  Needs an even P and SVDJ_STEP_QUAD_SECOND
+//                         as the mode of step s+1.
+//             QUAD_SECOND second step of a quad: launches nothing (its
+//                         first step did the work); only valid after QUAD.
 //   metric  device uint32[SVDJ_METRIC_WORDS] (svdj_stop.h): [0] max
 //           convergence value (float bits), [1] rotated pairs, [2..3] the
 //           underflow floor (double, svdj_set_norm_floor; 0 = off), [4] the
 //           largest |sin| of an applied rotation (float bits).
 //   tol_mode 0: rotate when |g_pq| > tol sqrt(g_pp g_qq) (relative, default);
 //            1: when |g_pq| > tol (the reference's absolute TOLERANCE test).
-//   mma     matrix-core mode: 0 native (f32 / f64 MFMA), 1 fp32 data on bf16
-//           MFMA with a 3-way bf16 split (6 products, fp32-level accuracy),
-//           2 fp32 data on bf16 MFMA with a 2-way split (3 products, ~2^-17).
-//           Both split modes apply Y = X + X (Q - I), the identity in fp32.
-//           Bit 8 (| 256): the quad Gram of quad steps with 2 bf16 parts (3
-//           products, couplings to ~2^-17) -- for sweeps far from convergence,
-//           where it only steers the rotation angles.
+//   mma     a flags word.  mma & SVDJ_MMA_MASK is the apply's matrix-core
+//           mode: SVDJ_MMA_NATIVE (f32 / f64 MFMA), SVDJ_MMA_BF16X6 (fp32 data
+//           on bf16 MFMA, 3-way bf16 split: 6 products, fp32-level accuracy),
+//           SVDJ_MMA_BF16X3 (2-way split: 3 products, ~2^-17).  Both split
+//           modes apply Y = X + X (Q - I), the identity in fp32.  Or'ed in:
+//             SVDJ_STEPS_GRAM2       the quad Gram of quad steps on 2 bf16
+//                                    parts (3 products, couplings to ~2^-17)
+//                                    -- for sweeps far from convergence, where
+//                                    it only steers the rotation angles;
+//             SVDJ_STEPS_SHARED_GPU  another chain runs concurrently on this
+//                                    GPU: the quad apply leaves it a share of
+//                                    the CUs (a smaller persistent grid).
+enum {
+  SVDJ_STEP_CROSS = 0,
+  SVDJ_STEP_FULL = 1,
+  SVDJ_STEP_CROSS_BIP = 2,
+  SVDJ_STEP_CROSS_ONLY = 3,
+  SVDJ_STEP_QUAD = 4,
+  SVDJ_STEP_QUAD_SECOND = 5
+};
+enum { SVDJ_MMA_NATIVE = 0, SVDJ_MMA_BF16X6 = 1, SVDJ_MMA_BF16X3 = 2 };
+enum { SVDJ_MMA_MASK = 0xff, SVDJ_STEPS_GRAM2 = 0x100, SVDJ_STEPS_SHARED_GPU = 0x200 };
+// bf16 parts of a matrix-core mode's operand split; 0: native, no split.
+static inline int svdj_mma_parts(int mma) {
+  return mma == SVDJ_MMA_BF16X6 ? 3 : mma == SVDJ_MMA_BF16X3 ? 2 : 0;
+}
+// inner_order codes of svdj_block_solve / svdj_dist_problem: the EVD of the
+// cross steps (SVDJ_STEP_CROSS / CROSS_BIP / CROSS_ONLY); AUTO resolves by
+// svdj_choose_inner_order.
+enum {
+  SVDJ_INNER_CYCLIC = 0,
+  SVDJ_INNER_BIPARTITE = 1,
+  SVDJ_INNER_CROSS = 2,
+  SVDJ_INNER_AUTO = 3
+};
+// The cross steps' mode for a resolved inner_order (not AUTO).
+static inline int svdj_cross_step_mode(int inner_order) {
+  return inner_order == SVDJ_INNER_CROSS    ? SVDJ_STEP_CROSS_ONLY
+         : inner_order == SVDJ_INNER_CYCLIC ? SVDJ_STEP_CROSS
+                                            : SVDJ_STEP_CROSS_BIP;
+}
 // Workspace size for steps of P pairs: svdj_block_workspace_bytes(); quad != 0
-// when the step list holds quad steps (modes 4/5: fp32, W = 64).
+// when the step list holds quad steps.
 size_t svdj_block_workspace_bytes(int dtype, int W, int P, int m_pad, int quad);
-// inner_order code (1 bipartite, 2 cross-only) for steps of `pairs` pairs of
-// W-wide blocks of data type `dtype` (0 fp32, 1 fp64): models/block.py
-// choose_inner_order.
+// inner_order code (SVDJ_INNER_BIPARTITE or SVDJ_INNER_CROSS) for steps of
+// `pairs` pairs of W-wide blocks of data type `dtype` (0 fp32, 1 fp64):
+// models/block.py choose_inner_order.
 int svdj_choose_inner_order(int dtype, int W, int pairs);
 // Default ("auto") matrix-core mode for dtype (0 fp32, 1 fp64) and block width
-// W: 1 (split bf16) for fp32 W = 64, else 0 (models/block.py choose_mma).
+// W: SVDJ_MMA_BF16X6 for fp32 W = 64, else SVDJ_MMA_NATIVE (models/block.py
+// choose_mma).
 int svdj_choose_mma(int dtype, int W);
 int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V,
                      int n_v, int ldv, void* D, const int32_t* pairs, int P,
@@ -92,11 +138,12 @@ int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V,
                      uint32_t* metric, int mma, void* stream);
 
 // Single-GPU block solve: round-robin over nb = ncols/W blocks (nb even),
-// first step of every sweep in full mode; inner_order 0 = cyclic EVD in every
-// step, 1 = bipartite EVD in the cross steps (mode 2), 2 = cross-only
-// bipartite EVD (mode 3).  stop_rule 1: a sweep also ends the iteration by
-// the second-order rule of svdj_stop.h (relative mode), 0: only a sweep
-// without rotations does.  Returns sweeps, <0 on error.
+// first step of every sweep SVDJ_STEP_FULL; inner_order (SVDJ_INNER_*) gives
+// the other steps' mode: CYCLIC SVDJ_STEP_CROSS, BIPARTITE SVDJ_STEP_CROSS_BIP,
+// CROSS SVDJ_STEP_CROSS_ONLY, AUTO by svdj_choose_inner_order.  stop_rule 1: a
+// sweep also ends the iteration by the second-order rule of svdj_stop.h
+// (relative mode), 0: only a sweep without rotations does.  Returns sweeps,
+// <0 on error.
 int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, void* V,
                      int n_v, int ldv, void* D, int ncols, double tol, int tol_mode,
                      int max_inner_sweeps, int max_sweeps, int inner_order, void* workspace,
@@ -115,7 +162,7 @@ int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_pad,
 // The six cross Grams of a quad step (fp32, W = 64; pairs in quad order,
 // P even): slabs (3P x nchunk x W x W) = the P pairs' Grams, then C_ad, C_bc,
 // C_ab, C_cd of every quad.  parts: 3 (exact to 2^-26) or 2 (2^-16, the
-// early-sweep Gram of svdj_block_steps' mma bit 8).
+// early-sweep Gram of svdj_block_steps' SVDJ_STEPS_GRAM2).
 int svdj_gram_quad(const void* A, int lda, int m_pad, const int32_t* pairs, int P,
                    int rows_per_chunk, void* slabs, int parts, void* stream);
 // X <- X Q for one pair of column blocks (X = 2W columns, leading dimension
@@ -133,7 +180,7 @@ int svdj_apply_q(int dtype, int W, int mma, void* X, int rows, int ld, const voi
 //           g < 4; i < 16; e < 8)
 //   skip1, skip2  device int32 [2 nq] each: quad q is skipped (its columns
 //           untouched, its Ts never read) when its four flags are all nonzero
-//   np      2 or 3 parts (mma 2 / 1 of svdj_block_steps)
+//   np      2 or 3 parts (svdj_mma_parts of svdj_block_steps' mma)
 //   grid    workgroups of the persistent kernel, >= 1 (256; 192 / 224 next to
 //           a second chain)
 //   cheap_log2  np = 3: a 128-row half of a 32-column tile of T - I whose
@@ -147,11 +194,11 @@ int svdj_apply_quad(void* A, int lda, int m_pad, void* V, int n_v, int ldv, cons
                     int nq, const void* Ts, const int32_t* skip1, const int32_t* skip2, int np,
                     int grid, int cheap_log2, uint32_t* work, void* stream);
 // The middle of a single step alone: everything a step of svdj_block_steps
-// runs after its Gram (mode 0 cyclic EVD, 1 full Gram + cyclic EVD, 2
-// bipartite EVD, 3 cross EVD + chunk pre-sum + Q build, selected by P and
-// nchunk as in a solve), from Gram slabs given by the caller.
-//   slabs   device, data type: P x nchunk x W x W (mode 1: 2W x 2W), summed
-//           over the nchunk chunks by the kernels
+// runs after its Gram (mode SVDJ_STEP_CROSS to SVDJ_STEP_CROSS_ONLY; the
+// variants of CROSS_ONLY's chunk pre-sum and Q build selected by P and nchunk
+// as in a solve), from Gram slabs given by the caller.
+//   slabs   device, data type: P x nchunk x W x W (SVDJ_STEP_FULL: 2W x 2W),
+//           summed over the nchunk chunks by the kernels
 //   D       device, squared column norms by block id; updated in place
 //   pairs   device int32 [P][2]; metric: device uint32[8] (svdj_stop.h),
 //           floor set

@@ -19,6 +19,9 @@ import torch
 
 from . import reference as ref
 from ._native import NativeError, cpu_lib, hip_check, hip_lib
+from .codes import (INNER_ORDERS, MMA_CODES, MMA_MASK, STEP_CROSS, STEP_CROSS_BIP,  # noqa: F401
+                    STEP_CROSS_ONLY, STEP_FULL, STEP_QUAD, STEP_QUAD_SECOND, STEPS_GRAM2,
+                    STEPS_SHARED_GPU)
 
 ROW_ALIGN = 128
 SUPPORTED_BLOCK = {torch.float32: (32, 64), torch.float64: (32, 64)}
@@ -27,7 +30,7 @@ SUPPORTED_BLOCK = {torch.float32: (32, 64), torch.float64: (32, 64)}
 # with a 3-way / 2-way operand split -- faster (memory-bound instead of
 # MFMA-bound at W=64) but NOT fp32-accurate on every input: the bf16 MFMA's
 # internal accumulation is biased when magnitudes mix (see block.hip).
-MMA_CODES = {"native": 0, "bf16x6": 1, "bf16x3": 2}
+# MMA_CODES and the other codes of svdj_hip.h: ops/codes.py.
 
 
 def mma_code(mma: str | int, dtype: torch.dtype) -> int:
@@ -294,19 +297,21 @@ def block_workspace(dtype, W, P, m_pad, device, slot: int = 0, pool: dict | None
     return ws
 
 
-INNER_ORDERS = ("cyclic", "bipartite", "cross")
+# the cross steps' mode and the CPU emulation's EVD order, by inner order
+_CROSS_MODE = {"cyclic": STEP_CROSS, "bipartite": STEP_CROSS_BIP, "cross": STEP_CROSS_ONLY}
+_EVD_ORDER = {mode: order for order, mode in _CROSS_MODE.items()}
 
 
 def step_modes(modes, inner_order="cyclic"):
-    """Plan modes (0 cross, 1 full) -> kernel modes: with the bipartite inner
-    ordering cross steps become mode 2 (block_evd.hpp EVD_BIP, W EVD steps instead
-    of 2W-1), with the cross-only ordering mode 3 (evd_cross_kernel: the
-    bipartite steps tracking only the cross couplings); full steps always use
-    the cyclic EVD."""
+    """Plan modes (STEP_CROSS, STEP_FULL, quad steps) -> kernel modes: with the
+    bipartite inner ordering cross steps become STEP_CROSS_BIP (block_evd.hpp
+    EVD_BIP, W EVD steps instead of 2W-1), with the cross-only ordering
+    STEP_CROSS_ONLY (evd_cross_kernel: the bipartite steps tracking only the
+    cross couplings); full steps always use the cyclic EVD."""
     if inner_order not in INNER_ORDERS:
         raise ValueError(f"inner_order must be one of {INNER_ORDERS}, got {inner_order!r}")
-    cm = {"cyclic": 0, "bipartite": 2, "cross": 3}[inner_order]  # "auto": resolve first
-    return [cm if int(x) == 0 else int(x) for x in modes]
+    cm = _CROSS_MODE[inner_order]  # "auto": resolve first
+    return [cm if int(x) == STEP_CROSS else int(x) for x in modes]
 
 
 def check_block(dtype, W):
@@ -320,12 +325,12 @@ def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_sl
                 inner_order="cyclic", gram_parts: int = 3, shared_gpu: bool = False):
     """Run ``len(modes)`` block steps on the current stream.  pairs: int32
     (steps, P, 2) on At's device (block indices local to At); modes: list of
-    0 (cross) / 1 (full) (see step_modes for ``inner_order``).  Chains running
+    STEP_* codes (see step_modes for ``inner_order``).  Chains running
     concurrently on different streams must use different ``ws_slot`` values.
-    ``gram_parts`` 2: the quad Gram on 2 bf16 parts (svdj_block_steps' mma bit
-    8; GPU only, the CPU emulation keeps the exact Gram).  ``shared_gpu``:
-    another chain runs concurrently on this GPU (bit 9: the quad apply leaves
-    it a quarter of the CUs)."""
+    ``gram_parts`` 2: the quad Gram on 2 bf16 parts (STEPS_GRAM2; GPU only,
+    the CPU emulation keeps the exact Gram).  ``shared_gpu``: another chain
+    runs concurrently on this GPU (STEPS_SHARED_GPU: the quad apply leaves it
+    a quarter of the CUs)."""
     modes = step_modes(modes, inner_order)
     _check_layout(At, m_pad)
     check_block(At.dtype, W)
@@ -334,7 +339,7 @@ def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_sl
         return
     if At.is_cuda:
         ws = block_workspace(At.dtype, W, P, m_pad, At.device, ws_slot, pool,
-                             quad=any(int(x) == 4 for x in modes))
+                             quad=STEP_QUAD in modes)
         md = (C.c_int32 * steps)(*[int(x) for x in modes])
         n_v = Vt.shape[1] if Vt is not None else 0
         ldv = Vt.stride(0) if Vt is not None else 0
@@ -342,24 +347,23 @@ def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_sl
             dtype_code(At.dtype), W, m_pad, _ptr(At), At.stride(0), _ptr(Vt), n_v, ldv,
             _ptr(D), _ptr(pairs), P, steps, md, float(tol), tol_mode_code(tol_mode),
             int(max_inner), _ptr(ws), ws.numel(), _ptr(metric),
-            mma_code(mma, At.dtype) | (256 if gram_parts == 2 else 0) | (512 if shared_gpu else 0),
-            _stream(At)), "block_steps")
+            mma_code(mma, At.dtype) | (STEPS_GRAM2 if gram_parts == 2 else 0)
+            | (STEPS_SHARED_GPU if shared_gpu else 0), _stream(At)), "block_steps")
     else:
         for s in range(steps):
-            if modes[s] == 5:  # second step of a quad: done with its first
+            if modes[s] == STEP_QUAD_SECOND:  # done with the quad's first step
                 continue
             stats = {"smax": 0.0}
-            if modes[s] == 4:
+            if modes[s] == STEP_QUAD:
                 mx, nrot = ref.quad_step(At[:, :m_pad], Vt, D, pairs[s], pairs[s + 1], W, tol,
                                          max_inner, tol_mode=tol_mode_code(tol_mode),
                                          floor=float(metric[2]) if metric.numel() > 2 else 0.0,
                                          stats=stats)
             else:
-                mx, nrot = ref.block_step(At[:, :m_pad], Vt, D, pairs[s], W, modes[s] == 1, tol,
+                mx, nrot = ref.block_step(At[:, :m_pad], Vt, D, pairs[s], W, modes[s] == STEP_FULL, tol,
                                           max_inner, tol_mode=tol_mode_code(tol_mode),
                                           floor=float(metric[2]) if metric.numel() > 2 else 0.0,
-                                          order={2: "bipartite", 3: "cross"}.get(modes[s],
-                                                                                 "cyclic"),
+                                          order=_EVD_ORDER.get(modes[s], "cyclic"),
                                           stats=stats)
             metric[0] = max(float(metric[0]), mx)
             metric[1] += nrot
@@ -630,6 +634,8 @@ __all__ = [
     "METRIC_WORDS", "read_stop", "metric_stop_values", "metric_work", "sweep_converged", "STOP_RULES",
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
     "block_workspace", "block_steps", "block_solve", "check_block", "MMA_CODES", "mma_code",
+    "STEP_CROSS", "STEP_FULL", "STEP_CROSS_BIP", "STEP_CROSS_ONLY", "STEP_QUAD", "STEP_QUAD_SECOND",
+    "MMA_MASK", "STEPS_GRAM2", "STEPS_SHARED_GPU",
     "apply_q", "apply_quad",
     "gram_cross", "gram_quad", "evd_alone", "quad_chain",
 ]

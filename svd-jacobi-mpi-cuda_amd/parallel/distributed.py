@@ -340,7 +340,7 @@ class DistributedBlockJacobi(Solver):
 
             def run_steps(pairs, modes, slot):
                 # quads of the quad steps issued (each runs the quad Gram): host count
-                nq = sum(1 for x in modes if int(x) == 4) * (pairs.shape[1] // 2)
+                nq = sum(1 for x in modes if int(x) == K.STEP_QUAD) * (pairs.shape[1] // 2)
                 work["gram_quads"] += nq
                 work["gram_quads2"] += nq if gram_parts[0] == 2 else 0
                 K.block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, cfg.max_inner_sweeps,

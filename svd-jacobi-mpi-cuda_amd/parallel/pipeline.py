@@ -36,6 +36,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from ..ops.codes import STEP_CROSS, STEP_FULL
 from .schedule import (quad_bipartite, quad_bipartite_modes, quad_round_robin,
                        quad_round_robin_modes, round_robin)
 from .spread import relay_chunk, resolve_exchange, spread_ops
@@ -99,7 +100,7 @@ def sweep_plan(P: int, k: int, xslot: np.ndarray, chains: int = 2, quad: bool = 
     if quad:
         rr, rr_modes = quad_round_robin(k), quad_round_robin_modes(k)
     else:
-        rr, rr_modes = round_robin(k), [1] + [0] * (k - 2)
+        rr, rr_modes = round_robin(k), [STEP_FULL] + [STEP_CROSS] * (k - 2)
     plan.items.append(Task("rr0", rr.copy(), rr_modes, 0, ((0, 0), (0, 1))))
     plan.items.append(Task("rr1", rr + k, rr_modes, 1, ((1, 0), (1, 1))))
     R = 2 * P - 1
@@ -113,7 +114,8 @@ def sweep_plan(P: int, k: int, xslot: np.ndarray, chains: int = 2, quad: bool = 
             if quad:
                 return Task(f"r{r}.{name}", quad_bipartite(xs, ys), quad_bipartite_modes(h), stream,
                             ((inc, ih), (stay, sh)))
-            return Task(f"r{r}.{name}", _bipartite(xs, ys), [0] * h, stream, ((inc, ih), (stay, sh)))
+            return Task(f"r{r}.{name}", _bipartite(xs, ys), [STEP_CROSS] * h, stream,
+                        ((inc, ih), (stay, sh)))
 
         nxt = int(xslot[r + 1]) if r + 1 < R else None
         if nxt is None:

@@ -17,6 +17,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ..ops._native import cpu_lib
+from ..ops.codes import STEP_CROSS, STEP_FULL, STEP_QUAD, STEP_QUAD_SECOND
 
 
 def _i32(shape):
@@ -89,9 +90,8 @@ def tournament(P: int) -> Tournament:
 # the four blocks (a, b, c, d): step s pairs (a, c), (b, d), step s+1 pairs
 # (a, d), (b, c), i.e. all cross pairs of the super-block pair {a, b} x
 # {c, d}.  Pair 2q / 2q+1 of both steps belong to quad q, in that
-# orientation (the kernels read the quad from the pair lists).  Mode codes:
-# 4 = first step of a quad (does both), 5 = its second step.
-QUAD_HEAD, QUAD_TAIL = 4, 5
+# orientation (the kernels read the quad from the pair lists).  Modes:
+# STEP_QUAD = first step of a quad (does both), STEP_QUAD_SECOND = its second.
 
 
 def quad_round_robin(nb: int) -> np.ndarray:
@@ -127,7 +127,7 @@ def quad_round_robin_py(nb: int) -> np.ndarray:
 
 
 def quad_round_robin_modes(nb: int) -> list:
-    return [1] + [QUAD_HEAD, QUAD_TAIL] * (nb // 2 - 1)
+    return [STEP_FULL] + [STEP_QUAD, STEP_QUAD_SECOND] * (nb // 2 - 1)
 
 
 def quad_bipartite(xs, ys) -> np.ndarray:
@@ -163,19 +163,19 @@ def quad_bipartite_py(xs, ys) -> np.ndarray:
 
 
 def quad_bipartite_modes(h: int) -> list:
-    return [QUAD_HEAD, QUAD_TAIL] * (h // 2)
+    return [STEP_QUAD, STEP_QUAD_SECOND] * (h // 2)
 
 
 def check_quad_steps(pairs: np.ndarray, modes) -> None:
-    """Raise ValueError unless every mode-4 step and the following mode-5
-    step hold quads in the orientation the kernels read."""
+    """Raise ValueError unless every STEP_QUAD step and the following
+    STEP_QUAD_SECOND step hold quads in the orientation the kernels read."""
     modes = [int(x) for x in modes]
     for s, md in enumerate(modes):
-        if md == QUAD_TAIL and (s == 0 or modes[s - 1] != QUAD_HEAD):
+        if md == STEP_QUAD_SECOND and (s == 0 or modes[s - 1] != STEP_QUAD):
             raise ValueError(f"step {s}: quad tail without head")
-        if md != QUAD_HEAD:
+        if md != STEP_QUAD:
             continue
-        if s + 1 >= len(modes) or modes[s + 1] != QUAD_TAIL:
+        if s + 1 >= len(modes) or modes[s + 1] != STEP_QUAD_SECOND:
             raise ValueError(f"step {s}: quad head without tail")
         p0, p1 = pairs[s], pairs[s + 1]
         if p0.shape[0] % 2:
@@ -233,7 +233,7 @@ class RoundPlan:
     ``pairs`` are LOCAL block indices into the GPU's resident buffer, which
     holds slot 0 in blocks [0, k) and slot 1 in blocks [k, 2k)."""
     pairs: np.ndarray   # (steps, k, 2)
-    modes: list         # per step 0 cross / 1 full
+    modes: list         # per step STEP_CROSS / STEP_FULL
 
 
 def distributed_sweep_plan(P: int, k: int) -> list:
@@ -245,8 +245,8 @@ def distributed_sweep_plan(P: int, k: int) -> list:
     between the two resident super-blocks.  Every block pair of the whole
     matrix is visited exactly once per sweep.
     """
-    plans = [RoundPlan(round_robin(2 * k), [1] + [0] * (2 * k - 2))]
+    plans = [RoundPlan(round_robin(2 * k), [STEP_FULL] + [STEP_CROSS] * (2 * k - 2))]
     bp = bipartite(k)
     for _ in range(1, 2 * P - 1):
-        plans.append(RoundPlan(bp, [0] * k))
+        plans.append(RoundPlan(bp, [STEP_CROSS] * k))
     return plans

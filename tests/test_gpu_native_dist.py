@@ -1,4 +1,4 @@
-"""Native distributed solver (csrc/dist/svdj_dist.cpp) through its fork launcher
+"""Native distributed solver (csrc/distributed/svdj_dist.cpp) through its fork launcher
 bin/svdj_dist_main: RCCL tournament, no Python and no torch in the ranks.
 
 On the one-GPU box the ranks share cuda:0 (--shared-gpu: each rank its own

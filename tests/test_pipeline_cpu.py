@@ -94,7 +94,7 @@ def _native_plan(P, g):
 
 @pytest.mark.parametrize("P", [1, 2, 3, 4, 8])
 def test_native_plan_matches_python(P):
-    """csrc/dist/svdj_dist.cpp builds the same sweep and issue order as the
+    """csrc/distributed/svdj_dist.cpp builds the same sweep and issue order as the
     Python executor (sweep_plan + issue_groups) on every rank."""
     tour = schedule.tournament(P)
 
