@@ -27,7 +27,8 @@ ARCH = os.environ.get("SVDJ_OFFLOAD_ARCH", "gfx950")
 
 CPU_SOURCES = sorted((CSRC / "cpu").glob("*.cpp"))
 HIP_SOURCES = sorted((CSRC / "hip").glob("*.hip"))
-HEADERS = sorted((CSRC / "include").glob("*.h")) + sorted((CSRC / "hip").glob("*.hpp"))
+HEADERS = (sorted((CSRC / "include").glob("*.h")) + sorted((CSRC / "hip").glob("*.hpp"))
+           + sorted((CSRC / "distributed").glob("*.hpp")))
 
 CPU_LIB = LIBDIR / "libsvdj_cpu.so"
 HIP_LIB = LIBDIR / "libsvdj_hip.so"
@@ -123,7 +124,8 @@ def build_driver(force: bool = False, verbose: bool = False) -> Path:
     return DRIVER_BIN
 
 
-DIST_SRC = CSRC / "distributed" / "svdj_dist.cpp"
+# dist_plan.cpp: the plan, host only; svdj_dist.cpp: the device engine (HIP + RCCL)
+DIST_SOURCES = [CSRC / "distributed" / "dist_plan.cpp", CSRC / "distributed" / "svdj_dist.cpp"]
 DIST_LIB = LIBDIR / "libsvdj_dist.so"
 DIST_DRIVER_SRC = CSRC / "driver" / "svdj_dist_main.cpp"
 DIST_DRIVER_BIN = PKG / "bin" / "svdj_dist_main"
@@ -136,11 +138,11 @@ def build_dist(force: bool = False, verbose: bool = False) -> Path:
     Returns the shared library ``DIST_LIB`` (the thing ``ctypes`` loads); the
     launcher is at ``DIST_DRIVER_BIN``."""
     cpu, hip = build_cpu(force, verbose), build_hip(force, verbose)
-    deps = [DIST_SRC, cpu, hip, Path(__file__)] + HEADERS
+    deps = DIST_SOURCES + [cpu, hip, Path(__file__)] + HEADERS
     if force or _stale(DIST_LIB, deps):
         tmp = DIST_LIB.with_suffix(".so.tmp")
         _run([_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", f"--offload-arch={ARCH}",
-              f"-I{CSRC / 'include'}", DIST_SRC, "-o", tmp, f"-L{LIBDIR}", "-lsvdj_hip",
+              f"-I{CSRC / 'include'}", *DIST_SOURCES, "-o", tmp, f"-L{LIBDIR}", "-lsvdj_hip",
               "-lsvdj_cpu", "-lrccl", "-Wl,-rpath,$ORIGIN"], verbose)
         os.replace(tmp, DIST_LIB)
     DIST_DRIVER_BIN.parent.mkdir(exist_ok=True)
@@ -159,19 +161,19 @@ ASAN_DIST_LIB = LIBDIR / "asan" / "libsvdj_dist.so"
 def build_dist_asan(force: bool = False, verbose: bool = False) -> Path:
     """AddressSanitizer + UBSan build of libsvdj_dist's host code (id-file
     handshake, plan and list builder, watchdog thread) into lib/asan/.  The
-    file holds no device code, so g++ compiles it against the HIP runtime
+    files hold no device code, so g++ compiles them against the HIP runtime
     headers, with the same sanitizer runtime as ``build_cpu(asan=True)``;
     it links the ASan libsvdj_cpu next to it and the regular libsvdj_hip.
     Load with SVDJ_DIST_LIB=<path> (tools/asan_cpu_tests.sh)."""
     cpu, hip = build_cpu(force, verbose, asan=True), build_hip(force, verbose)
     target = ASAN_DIST_LIB
-    if not force and not _stale(target, [DIST_SRC, cpu, hip, Path(__file__)] + HEADERS):
+    if not force and not _stale(target, DIST_SOURCES + [cpu, hip, Path(__file__)] + HEADERS):
         return target
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     tmp = target.with_suffix(".so.tmp")
     _run([os.environ.get("CXX", "g++"), "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
           "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-Wall", "-D__HIP_PLATFORM_AMD__",
-          f"-I{rocm}/include", f"-I{CSRC / 'include'}", DIST_SRC, "-o", tmp,
+          f"-I{rocm}/include", f"-I{CSRC / 'include'}", *DIST_SOURCES, "-o", tmp,
           f"-L{target.parent}", "-lsvdj_cpu", f"-L{LIBDIR}", "-lsvdj_hip", f"-L{rocm}/lib",
           "-lamdhip64", "-lrccl", "-Wl,-rpath,$ORIGIN:$ORIGIN/.."], verbose)
     os.replace(tmp, target)

@@ -55,6 +55,37 @@ def test_native_dist_launcher(np_, n, dtype, extra):
         assert rel < 2e-5 and ou < 5e-2 and ov < 2e-3, out
 
 
+@pytest.mark.parametrize("np_,n,quad,debug,issue", [
+    (1, 512, "on", None, "two chains, quad steps"),        # two chains, shared-GPU flag
+    (1, 512, "on", "merge=1", "merged chains, quad steps"),  # merged quad launches
+    (1, 512, "off", "merge=1", "merged chains  exchange"),  # merged single steps
+    (2, 1024, "on", None, "two chains, quad steps"),       # quad steps with exchanges
+])
+def test_native_issue_paths_smallest_shapes(np_, n, quad, debug, issue):
+    """Every issue path of the native engine at k = 4 blocks per super-block
+    (W = 64), the smallest shape with quad steps: the launcher's report names
+    the path that ran, and the solve meets the fp32 bounds of
+    test_native_dist_launcher."""
+    cmd = [_exe(), str(n), "--np", str(np_), "--dtype", "f32", "--input", "dense", "--block", "64",
+           "--quad", quad, "--verify", "--timeout", "120"]
+    if np_ > 1:
+        cmd.append("--shared-gpu")
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("SVDJ_DEBUG", None)
+    if debug:
+        env["SVDJ_DEBUG"] = debug
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=170, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert re.search(r"converged: [12]\b", out), out
+    assert f"issue: {issue}" in out and "super-block B: 256" in out, out
+    rel = _value(out, "||A-USVt||_F/||A||_F:")
+    ou = _value(out, "||U^TU-I||_F:")
+    ov = _value(out, "||V^TV-I||_F:")
+    print(f"rel {rel:.3e}  U orth {ou:.3e}  V orth {ov:.3e}")
+    assert rel < 2e-5 and ou < 5e-2 and ov < 2e-3, out
+
+
 def test_native_dist_rank_failure_stops_job():
     """An invalid problem on every rank (block width 48) must end the whole
     job with a non-zero status, not hang the other ranks."""
