@@ -1,7 +1,7 @@
 // Plan of the native distributed block one-sided Jacobi (svdj_dist.h), host
 // only; svdj_dist.cpp runs it with RCCL + the HIP block kernels of
-// libsvdj_hip, no Python.  Same plan as the Python executor
-// (parallel/pipeline.py, parallel/distributed.py):
+// libsvdj_hip, no Python.  Same plan as the Python engine
+// (parallel/plan.py; run by parallel/pipeline.py, parallel/distributed.py):
 //
 // Per sweep on GPU g (slots 0 and 1 hold super-blocks of k = B/W blocks,
 // each split in halves 0|1 of k/2 blocks; I = incoming slot, S = the other;
@@ -468,7 +468,7 @@ extern "C" int svdj_dist_issue_rules(int world, int dtype, int W, int mma, int k
   if (quad_mode < 0 || quad_mode > 2) return fail(-2, "quad %d (0 auto, 1 on, 2 off)", quad_mode);
   if (quad_mode == 1 && !quad_ok)
     return fail(-2, "quad steps need fp32, W = 64, a split-bf16 apply and k %% 4 == 0");
-  // models/block.py choose_quad, parallel/distributed.py choose_merged
+  // models/block.py choose_quad, choose_merged
   const int hk = k / 2;
   *quad = quad_ok && (quad_mode == 1 || (quad_mode == 0 && quad_size_rule(hk, m_pad, world)));
   const int force = svdj_debug_knob("merge", -1);  // A/B only (svdj_debug.h), world 1 only

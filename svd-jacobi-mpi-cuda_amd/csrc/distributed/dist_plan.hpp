@@ -24,7 +24,7 @@ struct Tour {  // svdj_tournament of P GPUs: 2P - 1 rounds
   int from(int r, int g) const { return recv_from[r * P + g]; }
 };
 
-// ---- sweep plan of one GPU (parallel/pipeline.py sweep_plan / issue_groups)
+// ---- sweep plan of one GPU (parallel/plan.py sweep_plan / issue_groups)
 // Halves are keyed slot*2 + half.  A task runs one template on a stream
 // (chain); a Send moves one half of one slot.
 enum { kTemplates = 10 };  // rr of slot 0, 1; cross[inc][ih][sh]
@@ -56,7 +56,7 @@ struct Template {
 // One GPU (canonical buffers: a local block id is its buffer block): the
 // parallel task pairs of the sweep -- rr0 + rr1, then the last round's
 // [T00 || T11] and [T01 || T10] -- concatenated step by step, the order of
-// pipeline.run_merged.  List i starts at pairs[off[i]].
+// pipeline.py run_merged.  List i starts at pairs[off[i]].
 struct PairLists {
   Template t[kTemplates];
   std::vector<int32_t> merged_pairs, merged_modes[3];
@@ -73,7 +73,7 @@ std::vector<std::pair<int, int>> placements(const int hv[2], int world);
 // its halves in buffers ba, bb; appended to out.
 void place_pairs(const Template& t, int k, int ba, int bb, std::vector<int32_t>& out);
 
-// ---- where the resident halves live (parallel/pipeline.py HalfLayout).
+// ---- where the resident halves live (parallel/plan.py HalfLayout).
 // Half buffers of hB columns: loc[slot][half] holds (slot, half); spare[h] is
 // the free buffer the next exchange of a half h receives into.  Buffers
 // {h, 2+h, 4+h} always hold (slot 0, h), (slot 1, h), spare.
@@ -86,7 +86,7 @@ struct Layout {
 // home (same rule as HalfLayout.moves_to_canonical).
 std::vector<std::pair<int, int>> moves_to_canonical(Layout& L);
 
-// Interval measure of union(waits) minus union(busy) (pipeline.exposed_time).
+// Interval measure of union(waits) minus union(busy) (plan.exposed_time).
 using Spans = std::vector<std::pair<double, double>>;
 double exposed_time(Spans waits, Spans busy);
 

@@ -388,7 +388,7 @@ int resolve_rules(svdj_dist_handle_t* h, const svdj_dist_problem* p) {
   h->spread = h->world > 2 && (p->exchange == 2 || (p->exchange == 0 && h->world >= 4));
   // quad steps from 32 pairs per chain step on any number of GPUs, merged
   // issue on one GPU from 64 pairs (32 with quad steps) -- the Python
-  // engine's rules: models/block.py choose_quad, distributed.py merged
+  // engine's rules: models/block.py choose_quad, choose_merged
   int quad = 0, merged = 0;
   const int rc = svdj_dist_issue_rules(p->world, p->dtype, W, p->mma, h->k, p->m_pad, p->quad,
                                        &quad, &merged);
@@ -777,7 +777,7 @@ extern "C" int svdj_dist_solve(svdj_dist_problem* p, void* sigma) {
   p->calib_direct_ms = h->calib_ms[0];
   p->calib_spread_ms = h->calib_ms[1];
   const auto t_solve = std::chrono::steady_clock::now();
-  // Quad Gram precision per sweep (parallel/distributed.py, the same rule):
+  // Quad Gram precision per sweep (distributed.py next_gram_parts, the same rule):
   // 2 bf16 parts (SVDJ_STEPS_GRAM2) while the previous sweep
   // rotated every pair; SVDJ_DEBUG gram2=0/1 forces it off / on (A/B).
   const long long nbt = 2LL * P * h->k, all_pairs = nbt * (nbt - 1) / 2;

@@ -4,7 +4,7 @@
 //   SVDJ_DEBUG="key=value[,key=value...]"
 //     merge=0|1            one-GPU merged issue of the two chains forced off/on
 //                          (world 1 only, both engines: svdj_dist_issue_rules,
-//                          parallel/distributed.py choose_merged)
+//                          models/block.py choose_merged)
 //     gram_chunks=N        row chunks of the single-step Gram (make_geometry)
 //     quad_gram_chunks=N   row chunks of the quad Gram (quad_geometry)
 //     stream_order=B       row-chunk dispatch order: bit 0 cross Gram chunks
@@ -17,7 +17,7 @@
 //                          row chunks when there are at least N (default 9)
 //     gram2=0|1            quad Gram on 2 bf16 parts forced off / on (default:
 //                          while the previous sweep rotated every pair; both
-//                          engines: parallel/distributed.py, svdj_dist_solve)
+//                          engines: next_gram_parts, svdj_dist_solve)
 //     apply_grid=N         quad apply persistent grid (default 256 = one
 //                          workgroup per CU)
 //     quad_pad=0           no extra zero columns for quad steps (both engines'

@@ -148,7 +148,7 @@ int svdj_dist_plan(int world, int rank, int32_t* out, int cap);
 // k % 4 == 0) and, on one GPU, the
 // merged issue (from 64 pairs per chain step, 32 with quad steps;
 // SVDJ_DEBUG merge=0/1 overrides, svdj_debug.h) -- models/block.py choose_quad and
-// parallel/distributed.py choose_merged.  Returns 0 or <0.
+// choose_merged.  Returns 0 or <0.
 int svdj_dist_issue_rules(int world, int dtype, int W, int mma, int k, int m_pad, int quad_mode,
                           int* quad, int* merged);
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from ..config import SVDOptions
+from ..config import SVDOptions, debug_knob
 from ..ops import kernels as K
 from ..utils.layout import pack_columns, pad_rows, round_up
 from .base import SVDResult, Solver, Timer
@@ -134,6 +134,39 @@ def resolve_quad(mode: str, dtype: torch.dtype, W: int, mma: str, k: int, P: int
                              f"(dtype={dtype}, W={W}, mma={mma}, k={k})")
         return True
     return choose_quad(dtype, W, mma, k, P, m_pad)
+
+
+def choose_merged(P: int, k: int, quad: bool) -> bool:
+    """One-GPU merged issue (PipelineExecutor.run_merged) for k W-blocks per
+    super-block: from 64 pairs per chain step; with quad steps from 16 to 31
+    pairs.  The reference's single-process path rotates one pair per launch
+    (main.cu:727-758); this is the opposite end: all of a step's pairs of
+    both chains in one launch.
+    On one GPU only, in both engines; SVDJ_DEBUG merge=0/1 overrides there
+    (config.debug_knob).  libsvdj_dist: svdj_dist_issue_rules.
+
+    Measured: one rank, no exchanges, >= 64 pairs per chain step (>= 32 with
+    quad steps): the two chains' parallel tasks merged into single launches
+    of twice the pairs, the EVD latency paid once per step
+    (profiles/r4_merge; from 64 pairs bitwise the two-chain solve, the Gram
+    keeps the chunking).  Single steps of 32 pairs keep the overlapped chains
+    (8192^2 merged +10 %); quad steps of 32 pairs merge well (12288^2 1747 ->
+    1677 ms, 8192^2 per sweep 39.4 -> 36.9 ms, profiles/r5_quad2), and so do
+    quad steps of 16 pairs (4096^2 135.4 -> 123.5 ms, profiles/r6_issue).
+    Since the quad apply leaves the concurrent chain CUs (profiles/r6_grid),
+    the two chains beat merging again from 32 quad pairs: 16384^2 3169-3187
+    -> 3034 ms (same 19 sweeps, bitwise the same result), 8192^2 30.4 -> 29.5
+    ms per sweep; 4096^2 (16 pairs) still merges, 110 vs 120 ms
+    (profiles/r6_merge).  With exchanges merging was slower at every P (round
+    6, 16384^2 P = 8: 51.9 ms per sweep merged, 50.6 merged with quad steps,
+    43.1 not merged; profiles/r6_issue/plan_p8)."""
+    if P != 1:
+        return False
+    force = debug_knob("merge")
+    if force is not None:
+        return force == 1
+    hk = k // 2
+    return 16 <= hk < 32 if quad else hk >= 64
 
 
 def resolve_inner_order(order: str, W: int, pairs_per_step: int,

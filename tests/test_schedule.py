@@ -89,6 +89,19 @@ def test_tournament_one_exchange_per_round(P):
     assert len(seen) == P * (2 * P - 1)
 
 
+def test_advance_placement_reproduces_the_tournament():
+    """plan.advance_placement (both Python engines' placement update), from
+    held[0] through rounds 1..2P-2, gives exactly the tournament's held[r]."""
+    from svdj.parallel import plan
+
+    for P in range(1, 9):
+        t = S.tournament(P)
+        phys = t.held[0].tolist()
+        for r in range(1, 2 * P - 1):
+            plan.advance_placement(t, r, phys)
+            assert phys == t.held[r].tolist(), (P, r)
+
+
 @pytest.mark.parametrize("P,k", [(1, 1), (1, 3), (2, 1), (2, 2), (3, 2), (4, 1), (4, 3)])
 def test_distributed_sweep_covers_every_block_pair_once(P, k):
     """Simulate placement + local plans: every W-block pair exactly once per sweep,
