@@ -75,6 +75,7 @@ class SolverConfig:
     # Measured on MI355X, 32768 x 8192 fp32: Jacobi on A directly 2.27-2.6 s; CholeskyQR2
     # + Jacobi on R + U = Q U_R 1.99 s (Householder QR via rocSOLVER geqrf: 5.4 s).
     qr_ratio: float = 2.0
+    panel_rows: int = 0             # svd_batched, precondition="qr": rows per QR panel (0: auto)
     chains: int = 2                 # block path: independent step chains on separate streams
     num_threads: int = 0            # CPU oracle OpenMP threads (0: default)
     progress: bool = False          # rank 0 prints one line per sweep to stderr

@@ -39,23 +39,10 @@
 // Barriers: one __syncthreads per step, reached by every thread (idle groups,
 // phantom and skipped pairs and converged or non-finite matrices fall
 // through to it); the sweep loop is counted and its break is uniform.
-#include "common.hpp"
+#include "batched_core.hpp"
 #include "svdj_hip.h"
 
-#include <limits>
-
 namespace svdj {
-
-constexpr int kBatchedLanes = 8;          // lanes per column pair
-constexpr int kBatchedMaxN = 64;          // columns (pairs x lanes <= 256 threads)
-constexpr int kBatchedMaxThreads = 256;
-constexpr size_t kBatchedLdsCap = 163840;  // one workgroup may take the CU's 160 KiB
-constexpr int kBatchedScratch = 128;      // sweep flags and reduction slots
-
-// Leading dimension of an LDS image with `rows` rows: >= rows, = 8 (mod 32).
-__host__ __device__ constexpr long batched_ld(long rows) {
-  return rows <= 8 ? 8 : (rows - 8 + 31) / 32 * 32 + 8;
-}
 
 // The one LDS layout: the size routine and the kernel both use it.
 struct BatchedLayout {
@@ -78,20 +65,7 @@ __host__ __device__ constexpr int batched_threads(int n) {
   return round_up((n + (n & 1)) / 2 * kBatchedLanes, SVDJ_WAVE);
 }
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v) {
-#pragma unroll
-  for (int o = kBatchedLanes / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, SVDJ_WAVE);
-  return v;
-}
-
-struct BatchedScratch {
-  float off[2][4];   // per sweep parity, per wave: largest convergence value
-  int rot[2][4];     // ... : any rotation applied
-  double red[2][4];  // per wave: load-time reductions ([0] amax, [1] dmax)
-};
-static_assert(sizeof(BatchedScratch) <= kBatchedScratch, "scratch");
-
+// The iteration itself (floor, sweeps, stop test, finalize) is batched_core.hpp.
 template <typename T>
 __global__ __launch_bounds__(kBatchedMaxThreads) void batched_svd_kernel(
     int m, int n, const T* __restrict__ A, long sb, long sr, long sc, T* __restrict__ U,
@@ -106,9 +80,8 @@ __global__ __launch_bounds__(kBatchedMaxThreads) void batched_svd_kernel(
   BatchedScratch* scr = reinterpret_cast<BatchedScratch*>(smem + L.scr_off);
   const int lda = (int)L.lda, ldv = (int)L.ldv;
 
-  const int tid = threadIdx.x, nthr = blockDim.x, nwave = nthr >> 6;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int grp = tid / kBatchedLanes, g = tid % kBatchedLanes, ngrp = nthr / kBatchedLanes;
+  const BatchedThread t = batched_thread();
+  const int tid = t.tid, nthr = t.nthr, nwave = t.nwave, lane = t.lane, wave = t.wave;
   const size_t b = blockIdx.x;
   const int total = m * n;
 
@@ -144,134 +117,14 @@ __global__ __launch_bounds__(kBatchedMaxThreads) void batched_svd_kernel(
   int ex = 0;
   if (am > 0.0 && am <= (double)std::numeric_limits<T>::max()) ex = ilogb(am);
 
-  // ---- scale, squared column norms, floor
-  T dmax = 0;
-  for (int j = grp; j < n; j += ngrp) {
-    T* a = As + j * lda;
-    T d = 0;
-    for (int i = g; i < m; i += kBatchedLanes) {
-      const T x = ex != 0 ? (T)scalbn(a[i], -ex) : a[i];
-      a[i] = x;
-      d += x * x;
-    }
-    d = group_sum(d);
-    dmax = fmax(dmax, d);
-  }
-  dmax = wave_max(dmax);
-  if (lane == 0) scr->red[1][wave] = (double)dmax;
-  __syncthreads();
-  double dm = 0.0;
-  for (int w = 0; w < nwave; ++w) dm = fmax(dm, scr->red[1][w]);
-  // svdj_set_norm_floor_scaled: max(m realmin, m realmin / eps * dmax)
-  const double tiny = (double)std::numeric_limits<T>::min();
-  const double eps = (double)std::numeric_limits<T>::epsilon();
-  const T floor_ = (T)fmax((double)m * tiny, (double)m * tiny / eps * dm);
-  // The relative test is scale free.  The absolute one is the caller's
-  // |a_p.a_q| > tol on the unscaled matrix: products of the scaled columns
-  // are 2^(-2 ex) times the caller's, and so is the threshold (0 or inf
-  // where it leaves T's range: every / no nonzero product exceeds it).
-  const T tol = (T)(tol_mode == 1 ? scalbn(tol_in, -2 * ex) : tol_in);
-
-  // ---- sweeps
-  const int N = n + (n & 1), half = N / 2, steps = N - 1;
-  int sweeps = 0;
-  float last_off = __builtin_inff();  // no sweep run: nothing measured
-  for (int sw = 0; sw < max_sweeps; ++sw) {
-    int rotated = 0;
-    float offmax = 0.0f;
-    for (int r = 0; r < steps; ++r) {
-      // pair of (step r, slot grp): round_robin_padded
-      int p = -1, q = -1;
-      if (grp < half) {
-        if (grp == 0) {
-          p = r;
-          q = N - 1;
-        } else {
-          int a = r + grp, c = r - grp + (N - 1);
-          if (a >= N - 1) a -= N - 1;
-          if (c >= N - 1) c -= N - 1;
-          p = a < c ? a : c;
-          q = a < c ? c : a;
-        }
-      }
-      const bool valid = p >= 0 && q < n;  // q >= n: the phantom position
-      T* ap = As + (valid ? p : 0) * lda;
-      T* aq = As + (valid ? q : 0) * lda;
-      const int rows = valid ? m : 0;
-      T alpha = 0, beta = 0, gamma = 0;
-      for (int i = g; i < rows; i += kBatchedLanes) {
-        const T x = ap[i], y = aq[i];
-        alpha += x * y;
-        beta += x * x;
-        gamma += y * y;
-      }
-      alpha = group_sum(alpha);
-      beta = group_sum(beta);
-      gamma = group_sum(gamma);
-      const T nrm = sqrt(beta) * sqrt(gamma);
-      if (valid && nrm > T(0)) {
-        const float cv = (float)(fabs(alpha) / nrm);
-        offmax = cv > offmax ? cv : offmax;  // drops NaN
-      }
-      bool rotate = (tol_mode == 1) ? (fabs(alpha) > tol)
-                                    : (nrm > T(0) && fabs(alpha) > tol * nrm);
-      rotate = rotate && valid && alpha != T(0) && fmin(beta, gamma) > floor_;
-      if (rotate) {
-        T c, s, t;
-        schur_rotation(alpha, beta, gamma, c, s, t);
-        rotated = 1;
-        for (int i = g; i < m; i += kBatchedLanes) {
-          const T x = ap[i], y = aq[i];
-          ap[i] = c * x - s * y;
-          aq[i] = s * x + c * y;
-        }
-        if (want_v) {
-          T* vp = Vs + p * ldv;
-          T* vq = Vs + q * ldv;
-          for (int i = g; i < n; i += kBatchedLanes) {
-            const T x = vp[i], y = vq[i];
-            vp[i] = c * x - s * y;
-            vq[i] = s * x + c * y;
-          }
-        }
-      }
-      if (r == steps - 1) {  // the sweep's flags ride on its last barrier
-        const int any = __any(rotated);
-        const float om = wave_max(offmax);
-        if (lane == 0) {
-          scr->rot[sw & 1][wave] = any;
-          scr->off[sw & 1][wave] = om;
-        }
-      }
-      __syncthreads();
-    }
-    int any = 0;
-    float om = 0.0f;
-    for (int w = 0; w < nwave; ++w) {
-      any |= scr->rot[sw & 1][w];
-      om = fmaxf(om, scr->off[sw & 1][w]);
-    }
-    sweeps = sw + 1;
-    last_off = om;
-    if (!any) break;  // uniform: every thread read the same flags
-  }
-
-  // ---- finalize: sigma = ||a_j|| (fp64 sum), u_j = a_j / sigma (sigma 0: as is)
-  for (int j = grp; j < n; j += ngrp) {
-    T* a = As + j * lda;
-    double acc = 0.0;
-    for (int i = g; i < m; i += kBatchedLanes) {
-      const double x = (double)a[i];
-      acc += x * x;
-    }
-    acc = group_sum(acc);
-    const double nrm = sqrt(acc);
-    if (g == 0) sig[j] = (T)scalbn(nrm, ex);
-    if (U != nullptr && nrm > 0.0) {
-      const T inv = (T)(1.0 / nrm);
-      for (int i = g; i < m; i += kBatchedLanes) a[i] *= inv;
-    }
-  }
+  // ---- scale, squared column norms, floor; sweeps; sigma and U
+  const T floor_ = batched_scale_floor(As, lda, m, n, ex, scr, t);
+  const T tol = batched_scaled_tol<T>(tol_in, tol_mode, ex);
+  int sweeps;
+  float last_off;
+  batched_sweeps(As, lda, Vs, ldv, m, n, want_v, tol, tol_mode, floor_, max_sweeps, scr, t,
+                 sweeps, last_off);
+  batched_finalize(As, lda, m, n, ex, sig, U != nullptr, t);
   __syncthreads();
 
   // ---- store: row-major outputs, consecutive lanes on consecutive columns

@@ -269,6 +269,39 @@ int svdj_batched_svd(int dtype, int batch, int m, int n, const void* A, long sb,
                      int max_sweeps, int32_t* sweeps, float* off, void* stream);
 
 // ---------------------------------------------------------------------------
+// Batched path for tall matrices (csrc/hip/batched_tall.hip): any m >= n with
+// 1 <= n <= 64 and m n < 2^31, one workgroup of 256 threads per matrix.  The
+// workgroup streams A through LDS in panels of `panel_rows` rows, folds each
+// into a resident n x n R with Householder reflectors (flat-tree TSQR), runs
+// the batched path's Jacobi on R with V, and streams back through the panels
+// to form U = Q U_R.  R and V always fit, so no row count is refused.
+//
+// The LDS bytes a workgroup takes at n columns and panels of panel_rows rows
+// (a positive multiple of 8), from the layout routine the kernel carves its
+// LDS with: R image, V image (want_v), two panel images, three per-reflector
+// slot arrays, sigma, scratch; 0: bad arguments or above the 163840-byte cap.
+size_t svdj_batched_tall_lds_bytes(int dtype, int n, int want_v, int panel_rows);
+// The panel height svdj_batched_tall_svd takes for panel_rows = 0: the largest
+// multiple of 8 that fits in half a CU's LDS (two workgroups per CU) if that
+// is at least 64 rows, else the largest that fits in all of it.
+int svdj_batched_tall_panel_rows(int dtype, int n, int want_v);
+// The solve.  A, S, V, tol, tol_mode, max_sweeps, sweeps, off: as
+// svdj_batched_svd (sweeps and off are those of the Jacobi on R).
+//   U       out, contiguous (batch, m, n) row-major, or NULL: not computed.
+//           Between the QR and the U stage it holds the reflector vectors.
+//   tau_ws  device workspace of batch x ceil(m / panel_rows) x n elements of
+//           the data type (the reflectors' taus); needed when U is not NULL
+//   panel_rows  0: svdj_batched_tall_panel_rows; else a positive multiple of 8
+// Returns 0; -2 with the error string set and nothing launched on a bad
+// argument (bad dtype, m < n, n > 64, m n >= 2^31, panel_rows negative, not a
+// multiple of 8 or too large for LDS, max_sweeps < 0, NULL A / S / sweeps /
+// off, U without tau_ws); batch == 0 returns 0 without any HIP call.
+int svdj_batched_tall_svd(int dtype, int batch, int m, int n, const void* A, long sb, long sr,
+                          long sc, void* U, void* S, void* V, void* tau_ws, int panel_rows,
+                          double tol, int tol_mode, int max_sweeps, int32_t* sweeps, float* off,
+                          void* stream);
+
+// ---------------------------------------------------------------------------
 // Post-processing / utilities.
 // V := I on an (n_v x ncols) column-major block (rows >= ncols zeroed).
 int svdj_set_identity(int dtype, void* V, int n_v, int ldv, int ncols, int col_offset, void* stream);

@@ -3,8 +3,12 @@
 Engine "kernel": one launch of csrc/hip/batched.hip, one workgroup per
 matrix with the matrix and V resident in LDS (a device input with at most 64
 columns after it is made tall, and a row count that fits the CU's LDS:
-``ops.kernels.batched_lds_bytes``).  Engine "loop": the single-matrix
-:func:`svd` per matrix -- on a CPU device the oracle -- so the API is total;
+``ops.kernels.batched_lds_bytes``).  Engine "qr_kernel": one launch of
+csrc/hip/batched_tall.hip, any row count at up to 64 columns (QR by row panels
+into an LDS-resident R, the same Jacobi on R, U = Q U_R); it runs only when
+the caller asks for it with ``precondition="qr"`` and the input, once made
+tall, has m > n (``panel_rows`` forces the panel height).  Engine "loop": the
+single-matrix :func:`svd` per matrix -- on a CPU device the oracle -- so the API is total;
 ``info["engine"]`` says which one ran.  An explicit ``method`` in the config
 (anything but "auto") is honoured: the loop engine runs that method per
 matrix.  S comes back in the working dtype on either engine (fp32 for bf16
@@ -25,11 +29,14 @@ class BatchedJacobi(Solver):
     name = "batched"
 
     def pick_engine(self, device, dtype, m: int, n: int, want_v: bool) -> str:
-        """"kernel" for a device problem (m >= n) inside the kernel's envelope."""
+        """"kernel" for a device problem (m >= n) inside the kernel's envelope;
+        "qr_kernel" for a tall one (m > n) when the config asks for the QR stage."""
         if self.config.method != "auto":  # the caller named a single-matrix solver
             return "loop"
         if torch.device(device).type != "cuda" or n < 1 or n > K.BATCHED_MAX_N:
             return "loop"
+        if self.config.precondition == "qr" and m > n:
+            return "qr_kernel"
         return "kernel" if K.batched_lds_bytes(dtype, m, n, want_v) > 0 else "loop"
 
     def solve(self, A, jobu=SVDOptions.AllVec, jobv=SVDOptions.AllVec,
@@ -47,8 +54,9 @@ class BatchedJacobi(Solver):
             jobu, jobv = jobv, jobu
         B, m, n = A3.shape
         want_u, want_v = jobu != SVDOptions.NoVec, jobv != SVDOptions.NoVec
-        tol = self.tolerance(cfg.precision_dtype(A), m)
         engine = self.pick_engine(device, dtype, m, n, want_v)
+        # the stop test sees the columns the Jacobi rotates: those of R (n rows) after a QR
+        tol = self.tolerance(cfg.precision_dtype(A), n if engine == "qr_kernel" else m)
         info = {"engine": engine, "tol": tol, "dtype": str(dtype), "device": str(device),
                 "batch": B, "transposed": wide}
         with Timer(device) as tm:
@@ -56,6 +64,8 @@ class BatchedJacobi(Solver):
                 out = self._empty(B, m, n, want_u, want_v, dtype, device)
             elif engine == "kernel":
                 out = self._kernel(A3, dtype, device, tol, want_u, want_v, info)
+            elif engine == "qr_kernel":
+                out = self._qr_kernel(A3, dtype, device, tol, want_u, want_v, info)
             else:
                 out = self._loop(A3, jobu, jobv, device)
         U, S, V, sweeps, off = out
@@ -87,17 +97,33 @@ class BatchedJacobi(Solver):
                 torch.zeros(B, dtype=torch.int32, device=device),
                 torch.zeros(B, dtype=torch.float32, device=device))
 
-    def _kernel(self, A3, dtype, device, tol, want_u, want_v, info):
-        cfg = self.config
+    @staticmethod
+    def _device_copy(A3, dtype, device, info):
         W = A3.to(device=device, dtype=dtype)  # keeps the strides of a dense view
         in_place = W.is_contiguous() or W.transpose(1, 2).is_contiguous()
         if not in_place:
             W = W.contiguous()
-        B, m, n = W.shape
         info["in_place"] = bool(in_place)
+        return W
+
+    def _kernel(self, A3, dtype, device, tol, want_u, want_v, info):
+        cfg = self.config
+        W = self._device_copy(A3, dtype, device, info)
+        B, m, n = W.shape
         info["lds_bytes"] = K.batched_lds_bytes(dtype, m, n, want_v)
         return K.batched_svd(W, tol, 1 if cfg.tol_mode == "absolute" else 0, cfg.max_sweeps,
                              want_u, want_v)
+
+    def _qr_kernel(self, A3, dtype, device, tol, want_u, want_v, info):
+        cfg = self.config
+        W = self._device_copy(A3, dtype, device, info)
+        B, m, n = W.shape
+        rows = cfg.panel_rows or K.batched_tall_balanced_rows(dtype, m, n, want_v)
+        info["panel_rows"] = rows
+        info["panels"] = -(-m // rows)
+        info["lds_bytes"] = K.batched_tall_lds_bytes(dtype, n, want_v, rows)
+        return K.batched_tall_svd(W, tol, 1 if cfg.tol_mode == "absolute" else 0, cfg.max_sweeps,
+                                  want_u, want_v, rows)
 
     def _loop(self, A3, jobu, jobv, device):
         from ..api import svd  # the single-matrix entry point (imports this module's package)

@@ -144,6 +144,12 @@ def hip_lib():
         _sig(lib, "svdj_batched_svd", c_int,
              [c_int, c_int, c_int, c_int, c_void_p, C.c_long, C.c_long, C.c_long, c_void_p,
               c_void_p, c_void_p, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p])
+        _sig(lib, "svdj_batched_tall_lds_bytes", c_size_t, [c_int, c_int, c_int, c_int])
+        _sig(lib, "svdj_batched_tall_panel_rows", c_int, [c_int, c_int, c_int])
+        _sig(lib, "svdj_batched_tall_svd", c_int,
+             [c_int, c_int, c_int, c_int, c_void_p, C.c_long, C.c_long, C.c_long, c_void_p,
+              c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_void_p, c_void_p,
+              c_void_p])
         _sig(lib, "svdj_set_identity", c_int,
              [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
         _sig(lib, "svdj_col_norms2", c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p])

@@ -628,8 +628,62 @@ def batched_svd(A: torch.Tensor, tol: float, tol_mode=0, max_sweeps: int = 60,
     return U, S, V, sweeps, off
 
 
+def batched_tall_lds_bytes(dtype: torch.dtype, n: int, want_v: bool = True,
+                           panel_rows: int = 8) -> int:
+    """LDS bytes one workgroup of the tall batched kernel takes at n columns
+    with panels of ``panel_rows`` rows (csrc/hip/batched_tall.hip
+    batched_tall_layout); 0: bad arguments, or more than 160 KiB."""
+    return int(hip_lib().svdj_batched_tall_lds_bytes(dtype_code(dtype), int(n), int(want_v),
+                                                     int(panel_rows)))
+
+
+def batched_tall_panel_rows(dtype: torch.dtype, n: int, want_v: bool = True) -> int:
+    """The panel height the tall batched kernel chooses at n columns (0: n
+    outside 1..64)."""
+    return int(hip_lib().svdj_batched_tall_panel_rows(dtype_code(dtype), int(n), int(want_v)))
+
+
+def batched_tall_balanced_rows(dtype: torch.dtype, m: int, n: int, want_v: bool = True) -> int:
+    """Panel height for m rows: as many panels as the kernel's own choice
+    needs, of equal height (a multiple of 8), so that the zero padding of the
+    last one stays under 8 rows per panel."""
+    top = batched_tall_panel_rows(dtype, n, want_v)
+    if top <= 0:
+        return 0
+    panels = -(-int(m) // top)
+    return min(top, (-(-int(m) // panels) + 7) // 8 * 8)
+
+
+def batched_tall_svd(A: torch.Tensor, tol: float, tol_mode=0, max_sweeps: int = 60,
+                     want_u: bool = True, want_v: bool = True, panel_rows: int = 0):
+    """SVD of every matrix of the device tensor ``A`` (batch, m, n), m >= n,
+    n <= 64, any m, in one launch on the current stream: QR by row panels into
+    an LDS-resident R, Jacobi on R, U = Q U_R (csrc/hip/batched_tall.hip).
+    ``panel_rows`` 0: the kernel's choice; a positive multiple of 8 forces
+    it.  Returns what :func:`batched_svd` returns."""
+    if A.dim() != 3 or not A.is_cuda:
+        raise ValueError("batched_tall_svd: a (batch, m, n) device tensor")
+    B, m, n = A.shape
+    dev, dt = A.device, A.dtype
+    rows = int(panel_rows) or batched_tall_panel_rows(dt, n, want_v)
+    U = torch.empty(B, m, n, dtype=dt, device=dev) if want_u else None
+    S = torch.empty(B, n, dtype=dt, device=dev)
+    V = torch.empty(B, n, n, dtype=dt, device=dev) if want_v else None
+    tau = (torch.empty(B, -(-m // rows), n, dtype=dt, device=dev)
+           if want_u and rows > 0 else None)
+    sweeps = torch.empty(B, dtype=torch.int32, device=dev)
+    off = torch.empty(B, dtype=torch.float32, device=dev)
+    hip_check(hip_lib().svdj_batched_tall_svd(
+        dtype_code(dt), B, m, n, _ptr(A), A.stride(0), A.stride(1), A.stride(2), _ptr(U), _ptr(S),
+        _ptr(V), _ptr(tau), int(panel_rows), float(tol), tol_mode_code(tol_mode), int(max_sweeps),
+        _ptr(sweeps), _ptr(off), _stream(A)), "batched_tall_svd")
+    return U, S, V, sweeps, off
+
+
 __all__ = [
     "batched_lds_bytes", "batched_threads", "batched_svd", "BATCHED_MAX_N",
+    "batched_tall_lds_bytes", "batched_tall_panel_rows", "batched_tall_balanced_rows",
+    "batched_tall_svd",
     "NativeError", "ROW_ALIGN", "SUPPORTED_BLOCK", "INNER_ORDERS", "step_modes", "dtype_code", "new_metric", "reset_metric", "set_norm_floor",
     "METRIC_WORDS", "read_stop", "metric_stop_values", "metric_work", "sweep_converged", "STOP_RULES",
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
