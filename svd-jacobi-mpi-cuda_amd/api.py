@@ -68,6 +68,8 @@ def svd(A: torch.Tensor, jobu=SVDOptions.AllVec, jobv=SVDOptions.AllVec,
         if res.U is not None:
             res.U = pre.apply_q(Q, Lt, res.U.to(Q.device)).to(res.U.dtype)
         res.info["precondition"] = "qr"
+        # which factorisation ran: CholeskyQR2 leaves its second factor to apply_q
+        res.info["qr"] = "householder" if Lt is None else "cholqr2"
     res.info["flops"] = pre.flops(mm, nn, res.sweeps, Q is not None)
     if transposed:
         res.U, res.V = res.V, res.U
