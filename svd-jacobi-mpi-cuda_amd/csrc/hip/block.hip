@@ -167,32 +167,48 @@ extern "C" int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, v
   return rc ? rc : sweeps;
 }
 
-// Cross Gram alone (tests / kernel A/B): slabs (P x nchunk x W x W) of
-// A_bi^T A_bj for the device pair list, with the given row chunking, through
-// launch_gram (fp32 only).
+// The Gram of a single step alone (tests / kernel A/B): launch_gram on the
+// device pair list with the given row chunking, every case of it -- fp32 and
+// fp64, W = 32 and 64, mode SVDJ_STEP_FULL (slabs P x nchunk x 2W x 2W of
+// [A_bi A_bj]^T [A_bi A_bj]) or SVDJ_STEP_CROSS (P x nchunk x W x W of
+// A_bi^T A_bj; the other cross modes run the same Gram).
+extern "C" int svdj_gram(int dtype, int W, int mode, const void* A, int lda, int m_pad,
+                         const int32_t* pairs, int P, int rows_per_chunk, void* slabs,
+                         void* stream) {
+  if (m_pad <= 0 || m_pad % SVDJ_ROW_ALIGN || lda < m_pad || P <= 0 || rows_per_chunk <= 0 ||
+      rows_per_chunk % SVDJ_ROW_ALIGN || !A || !pairs || !slabs) {
+    set_error("svdj_gram: bad m_pad/lda/P/rows %d/%d/%d/%d or a null pointer", m_pad, lda, P,
+              rows_per_chunk);
+    return -2;
+  }
+  if (mode != SVDJ_STEP_CROSS && mode != SVDJ_STEP_FULL) {
+    set_error("svdj_gram: mode %d (SVDJ_STEP_CROSS or SVDJ_STEP_FULL)", mode);
+    return -2;
+  }
+  if (dtype == 0 && W == 64 && lda % 4) {  // 16-byte loads along the rows of a column
+    set_error("svdj_gram: lda %d must be a multiple of 4", lda);
+    return -2;
+  }
+  return dispatch_tw(dtype, W, [&](auto t, auto w) {
+    using T = decltype(t);
+    const int32_t modes[1] = {mode};  // c.modes: read by launch_gram below, not after it
+    Chain<T> c{};  // the fields launch_gram reads
+    c.A = const_cast<T*>((const T*)A);  // only read by the Gram
+    c.lda = lda; c.m_pad = m_pad; c.pairs = pairs; c.P = P; c.steps = 1; c.modes = modes;
+    c.st = (hipStream_t)stream;
+    c.g.grows = rows_per_chunk;
+    c.g.gchunks = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
+    c.slabs = (T*)slabs;
+    return launch_gram<T, decltype(w)::value>(c, 0);
+  });
+}
+
+// The cross Gram alone: svdj_gram with SVDJ_STEP_CROSS.
 extern "C" int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_pad,
                                const int32_t* pairs, int P, int rows_per_chunk, void* slabs,
                                void* stream) {
-  if (m_pad <= 0 || m_pad % SVDJ_ROW_ALIGN || lda < m_pad || P <= 0 || rows_per_chunk <= 0 ||
-      rows_per_chunk % SVDJ_ROW_ALIGN) {
-    set_error("svdj_gram_cross: bad m_pad/lda/P/rows %d/%d/%d/%d", m_pad, lda, P, rows_per_chunk);
-    return -2;
-  }
-  if (dtype != 0 || (W != 32 && W != 64)) {
-    set_error("svdj_gram_cross: unsupported dtype=%d W=%d", dtype, W);
-    return -3;
-  }
-  if (W == 64 && lda % 4) {
-    set_error("svdj_gram_cross: lda %d must be a multiple of 4", lda);
-    return -2;
-  }
-  Chain<float> c{};  // the fields launch_gram reads (no modes: a cross step)
-  c.A = const_cast<float*>((const float*)A);  // only read by the Gram
-  c.lda = lda; c.m_pad = m_pad; c.pairs = pairs; c.P = P; c.st = (hipStream_t)stream;
-  c.g.grows = rows_per_chunk;
-  c.g.gchunks = (m_pad + rows_per_chunk - 1) / rows_per_chunk;
-  c.slabs = (float*)slabs;
-  return W == 64 ? launch_gram<float, 64>(c, 0) : launch_gram<float, 32>(c, 0);
+  return svdj_gram(dtype, W, SVDJ_STEP_CROSS, A, lda, m_pad, pairs, P, rows_per_chunk, slabs,
+                   stream);
 }
 
 // The six cross Grams of a quad step (fp32, W = 64) alone (tests / kernel

@@ -155,8 +155,15 @@ int svdj_reset_metric(uint32_t* metric, void* stream);
 
 // Diagnostic hooks.  Each runs one stage of a step through the launcher a
 // solve calls for it (block_launch.hpp launch_*), on buffers given by the caller.
-// Cross Gram slabs (P x nchunk x W x W) of A_bi^T A_bj
-// for a device pair list with the given row chunking (fp32).
+// The Gram of one step for a device pair list with the given row chunking
+// (rows_per_chunk a multiple of SVDJ_ROW_ALIGN; chunk c = rows [c rows,
+// min(m_pad, (c + 1) rows))), unsummed: mode SVDJ_STEP_CROSS slabs (P x nchunk
+// x W x W) of A_bi^T A_bj, SVDJ_STEP_FULL (P x nchunk x 2W x 2W) of
+// [A_bi A_bj]^T [A_bi A_bj].  fp32 and fp64, W = 32 and 64 (fp32 W = 64: lda a
+// multiple of 4).
+int svdj_gram(int dtype, int W, int mode, const void* A, int lda, int m_pad,
+              const int32_t* pairs, int P, int rows_per_chunk, void* slabs, void* stream);
+// svdj_gram with SVDJ_STEP_CROSS.
 int svdj_gram_cross(int dtype, int W, const void* A, int lda, int m_pad,
                     const int32_t* pairs, int P, int rows_per_chunk, void* slabs, void* stream);
 // The six cross Grams of a quad step (fp32, W = 64; pairs in quad order,

@@ -372,24 +372,48 @@ def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_sl
                 metric[4] += stats.get("ncols", 0)
 
 
-def gram_cross(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
-               rows_per_chunk: int) -> torch.Tensor:
-    """Cross Gram A_bi^T A_bj of every (bi, bj) in ``pairs`` (P, 2) on the
-    device, split over row chunks as in a block step; returns the chunk slabs
-    (P, nchunk, W, W)."""
+def _slabs(shape, At, out):
+    """The Gram hooks' result: a new tensor, or ``out`` (tests: pre-filled, so
+    that an entry the kernel leaves unwritten shows)."""
+    if out is None:
+        return torch.empty(*shape, dtype=At.dtype, device=At.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != At.dtype or out.device != At.device or \
+            not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {At.dtype} tensor of shape {tuple(shape)} on "
+                         f"{At.device}")
+    return out
+
+
+def _gram(At, m_pad, pairs, W, rows_per_chunk, mode, out, what):
     _check_layout(At, m_pad)
     pairs = pairs.to(torch.int32).contiguous().to(At.device)
     P = pairs.shape[0]
     nchunk = -(-m_pad // rows_per_chunk)
-    slabs = torch.empty(P, nchunk, W, W, dtype=At.dtype, device=At.device)
-    hip_check(hip_lib().svdj_gram_cross(dtype_code(At.dtype), W, _ptr(At), At.stride(0), m_pad,
-                                        _ptr(pairs), P, rows_per_chunk, _ptr(slabs), _stream(At)),
-              "gram_cross")
+    N = 2 * W if mode == STEP_FULL else W
+    slabs = _slabs((P, nchunk, N, N), At, out)
+    hip_check(hip_lib().svdj_gram(dtype_code(At.dtype), W, mode, _ptr(At), At.stride(0), m_pad,
+                                  _ptr(pairs), P, rows_per_chunk, _ptr(slabs), _stream(At)), what)
     return slabs
 
 
+def gram_cross(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
+               rows_per_chunk: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Cross Gram A_bi^T A_bj of every (bi, bj) in ``pairs`` (P, 2) on the
+    device (fp32 or fp64), split over row chunks as in a block step; returns
+    the chunk slabs (P, nchunk, W, W)."""
+    return _gram(At, m_pad, pairs, W, rows_per_chunk, STEP_CROSS, out, "gram_cross")
+
+
+def gram_full(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
+              rows_per_chunk: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Full Gram [A_bi A_bj]^T [A_bi A_bj] of every (bi, bj) in ``pairs``, the
+    Gram of a STEP_FULL step; returns the chunk slabs (P, nchunk, 2W, 2W)."""
+    return _gram(At, m_pad, pairs, W, rows_per_chunk, STEP_FULL, out, "gram_full")
+
+
 def gram_quad(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
-              rows_per_chunk: int, parts: int = 3) -> torch.Tensor:
+              rows_per_chunk: int, parts: int = 3,
+              out: torch.Tensor | None = None) -> torch.Tensor:
     """The six cross Grams of a quad step (fp32, W = 64): ``pairs`` (P, 2) on
     the device in quad order ((a, c), (b, d) per quad).  Returns the slabs
     (3P, nchunk, W, W): the P pairs' Grams, then C_ad, C_bc, C_ab, C_cd of
@@ -401,7 +425,7 @@ def gram_quad(At: torch.Tensor, m_pad: int, pairs: torch.Tensor, W: int,
     pairs = pairs.to(torch.int32).contiguous().to(At.device)
     P = pairs.shape[0]
     nchunk = -(-m_pad // rows_per_chunk)
-    slabs = torch.empty(3 * P, nchunk, W, W, dtype=At.dtype, device=At.device)
+    slabs = _slabs((3 * P, nchunk, W, W), At, out)
     hip_check(hip_lib().svdj_gram_quad(_ptr(At), At.stride(0), m_pad, _ptr(pairs), P,
                                        rows_per_chunk, _ptr(slabs), int(parts), _stream(At)),
               "gram_quad")
@@ -691,5 +715,5 @@ __all__ = [
     "STEP_CROSS", "STEP_FULL", "STEP_CROSS_BIP", "STEP_CROSS_ONLY", "STEP_QUAD", "STEP_QUAD_SECOND",
     "MMA_MASK", "STEPS_GRAM2", "STEPS_SHARED_GPU",
     "apply_q", "apply_quad",
-    "gram_cross", "gram_quad", "evd_alone", "quad_chain",
+    "gram_cross", "gram_full", "gram_quad", "evd_alone", "quad_chain",
 ]
