@@ -44,7 +44,50 @@ struct alignas(2 * sizeof(T)) Pair2 {
 // workgroup).  8, 16 and 32 measured the same (8-GPU rank plan 59.5 / 60.0 /
 // 59.9 ms per sweep): the slab sum is not what the EVD's latency is made of.
 #define SVDJ_EVD_SLAB_UNROLL 8
-__host__ __device__ constexpr int evd_threads(int) { return 1024; }
+constexpr int kEvdThreads = 1024;
+
+// ------------------------------------------------------------ split-K slab sum
+// A Gram arrives as nchunk slabs (one per row chunk of the data), `stride`
+// elements apart.  THE sum of one 16-byte vector of them, at element `off` of
+// the first slab: fp64 accumulators, chunk order, rounded once by the caller.
+// Every consumer of slabs -- both EVD kernels, quad_update_kernel and
+// slab_reduce_kernel -- sums with this function, so a pre-summed slab
+// (slab_reduce_kernel, nchunk = 1 afterwards) is bitwise what the consumer
+// would have summed from the chunks itself.  UNROLL: chunk loads in flight
+// (#pragma unroll UNROLL; 0 leaves the loop to the compiler).
+template <typename T, int N>
+using vec = T __attribute__((ext_vector_type(N)));
+template <int UNROLL, typename T>
+__device__ __forceinline__ vec<double, 16 / (int)sizeof(T)> slab_sum(const T* base, int off,
+                                                                    int stride, int nchunk) {
+  constexpr int EV = 16 / (int)sizeof(T);
+  vec<double, EV> acc = 0.0;
+  auto add = [&](int k) {
+    const auto v = *reinterpret_cast<const vec<T, EV>*>(base + (size_t)k * stride + off);
+    acc += __builtin_convertvector(v, vec<double, EV>);
+  };
+  if constexpr (UNROLL > 0) {
+#pragma unroll UNROLL
+    for (int k = 0; k < nchunk; ++k) add(k);
+  } else {
+    for (int k = 0; k < nchunk; ++k) add(k);
+  }
+  return acc;
+}
+
+// Slabs summed over their chunks ahead of their consumers, spread over many
+// workgroups: with many chunks (few pairs per launch: 64 chunks at 4 quads)
+// the latency-bound consumers, one workgroup per pair, then read one slab
+// instead of all chunks (8-GPU plan: quad_update 334 us per launch reading 64
+// chunks, profiles/r5_quad2).  W = 64, fp32: in = [slab][gch][W * W].
+constexpr int kRedThreads = 256;
+__global__ __launch_bounds__(kRedThreads) void slab_reduce_kernel(const float* __restrict__ in,
+                                                                  int gch, float* __restrict__ out) {
+  constexpr int W = 64;
+  const int slab = blockIdx.x, e = 4 * (blockIdx.y * kRedThreads + threadIdx.x);
+  const auto s = slab_sum<8>(in + (size_t)slab * gch * W * W, e, W * W, gch);
+  *reinterpret_cast<f32x4*>(out + (size_t)slab * W * W + e) = __builtin_convertvector(s, f32x4);
+}
 
 // Lane i <- lane i-1 / i+1 across the wave (DPP wave_shr:1 / wave_shl:1).
 // The edge lane receives 0 (bound_ctrl); every caller overwrites the edge
@@ -162,80 +205,11 @@ __device__ __forceinline__ double rsqrt64(double x) {
   return y;
 }
 
-// Circle-method players of slot a at step st (the same movement as the DPP
-// shifts of the register Q: firsts move right, seconds left, player N-1 fixed
-// in slot 0).  Ring of R = N-1 positions; slot a >= 1 has its first at
-// position a-1 and its second at 2W-2-a; the player at position x after st
-// steps is ((x - st) mod R + 1) mod R.  Checked against the DPP movement by
-// tests/test_schedule.py::test_evd_ring_matches_dpp_movement.
-template <int W>
-__device__ __forceinline__ int ring_player(int pos, int st) {
-  constexpr int R = 2 * W - 1;
-  int x = pos - st;
-  x += x < 0 ? R : 0;
-  return x + 1 == R ? 0 : x + 1;
-}
-template <int W>
-__device__ __forceinline__ void ring_slot(int a, int st, int& p, int& q) {
-  p = a == 0 ? 2 * W - 1 : ring_player<W>(a - 1, st);
-  q = ring_player<W>(2 * W - 2 - a, st);
-}
-// ---- position space.  The circle method fixes WHERE things happen and moves
-// the players: ring positions 0..R-1 (R = 2W-1) plus the fixed position R of
-// player N-1; slot a >= 1 owns positions (a-1, 2W-2-a), slot 0 owns (R, R-1).
-// Every step each ring player advances one position, so an off-diagonal G
-// entry at positions (P1, P2) moves to (P1+1, P2+1) (mod R; R stays R).
-// Storing G by POSITION pair -- double-buffered, the update phase reads step
-// st's buffer at the block's positions and writes the moved entries into the
-// other buffer -- makes every thread's LDS addresses static for the whole
-// kernel: no per-step index arithmetic.  Which entries of a block hold the
-// next step's pairs is static as well (next_meeting).
-template <int W>
-__host__ __device__ constexpr int pos_next(int P) {
-  return P == 2 * W - 1 ? P : (P + 1 == 2 * W - 1 ? 0 : P + 1);
-}
-template <int W>
-__host__ __device__ constexpr int ring_slot_of(int pos) {  // slot of a ring position
-  return pos == 2 * W - 1 ? 0 : (pos <= W - 2 ? pos + 1 : 2 * W - 2 - pos);
-}
-// Where the players now at positions (P1, P2) meet at the NEXT step: returns
-// 2*slot + (the player at P1 is that slot's first), or -1 if they do not.
-template <int W>
-__host__ __device__ constexpr int next_meeting(int P1, int P2) {
-  constexpr int R = 2 * W - 1;
-  if (P1 == R || P2 == R) {
-    const int o = P1 == R ? P2 : P1;
-    if (pos_next<W>(o) != R - 1) return -1;  // N-1 meets the second of slot 0
-    return P1 == R ? 1 : 0;
-  }
-  const int n1 = pos_next<W>(P1), n2 = pos_next<W>(P2);
-  if (ring_slot_of<W>(n1) != ring_slot_of<W>(n2)) return -1;
-  return 2 * ring_slot_of<W>(n1) + (n1 <= W - 2 ? 1 : 0);
-}
 // Packed strict upper triangle of an N x N position-pair matrix.
 template <int N>
 __host__ __device__ constexpr int tri_idx(int i, int j) {
   const int a = i < j ? i : j, b = i < j ? j : i;
   return a * N - a * (a + 1) / 2 + (b - a - 1);
-}
-// Position of player x at step 0 (inverse of ring_slot at st = 0).
-template <int W>
-__host__ __device__ constexpr int pos0(int x) {
-  return x == 2 * W - 1 ? 2 * W - 1 : (x == 0 ? 2 * W - 2 : x - 1);
-}
-template <int W>
-__host__ __device__ constexpr int slot_first_pos(int a) { return a == 0 ? 2 * W - 1 : a - 1; }
-template <int W>
-__host__ __device__ constexpr int slot_second_pos(int a) { return 2 * W - 2 - a; }
-template <int W>
-__host__ __device__ constexpr int block_duty(int a, int b) {  // 256*e + meeting, or -1
-  for (int e = 0; e < 4; ++e) {
-    const int x = (e >> 1) ? slot_second_pos<W>(a) : slot_first_pos<W>(a);
-    const int y = (e & 1) ? slot_second_pos<W>(b) : slot_first_pos<W>(b);
-    const int mt = next_meeting<W>(x, y);
-    if (mt >= 0) return 256 * e + mt;
-  }
-  return -1;
 }
 
 // ---- inner orderings.  The kernel below is written against an ordering
@@ -258,23 +232,60 @@ __host__ __device__ constexpr int block_duty(int a, int b) {  // 256*e + meeting
 enum { EVD_CYCLIC = 0, EVD_BIP = 1 };
 template <int W, int ORD>
 struct Ord;
+// Position space.  The circle method fixes WHERE things happen and moves the
+// players: ring positions 0..R-1 (R = 2W-1) plus the fixed position R of
+// player N-1; slot a >= 1 owns positions (a-1, 2W-2-a), slot 0 owns (R, R-1).
+// Every step each ring player advances one position, so an off-diagonal G
+// entry at positions (P1, P2) moves to (P1+1, P2+1) (mod R; R stays R).
+// Storing G by POSITION pair -- double-buffered, the update phase reads step
+// st's buffer at the block's positions and writes the moved entries into the
+// other buffer -- makes every thread's LDS addresses static for the whole
+// kernel: no per-step index arithmetic.  Which entries of a block hold the
+// next step's pairs is static as well (next_meeting).
 template <int W>
 struct Ord<W, EVD_CYCLIC> {
   static constexpr int R = 2 * W - 1;
-  __host__ __device__ static constexpr int pos_next(int P) { return svdj::pos_next<W>(P); }
+  __host__ __device__ static constexpr int pos_next(int P) {
+    return P == R ? P : (P + 1 == R ? 0 : P + 1);
+  }
   __host__ __device__ static constexpr int prev_pos(int P) {
-    return P == 2 * W - 1 ? P : (P == 0 ? 2 * W - 2 : P - 1);
+    return P == R ? P : (P == 0 ? R - 1 : P - 1);
   }
-  __host__ __device__ static constexpr int slot_of(int pos) { return ring_slot_of<W>(pos); }
+  __host__ __device__ static constexpr int slot_of(int pos) {  // slot of a position
+    return pos == R ? 0 : (pos <= W - 2 ? pos + 1 : 2 * W - 2 - pos);
+  }
+  // Where the players now at positions (P1, P2) meet at the NEXT step: returns
+  // 2*slot + (the player at P1 is that slot's first), or -1 if they do not.
   __host__ __device__ static constexpr int next_meeting(int P1, int P2) {
-    return svdj::next_meeting<W>(P1, P2);
+    if (P1 == R || P2 == R) {
+      const int o = P1 == R ? P2 : P1;
+      if (pos_next(o) != R - 1) return -1;  // N-1 meets the second of slot 0
+      return P1 == R ? 1 : 0;
+    }
+    const int n1 = pos_next(P1), n2 = pos_next(P2);
+    if (slot_of(n1) != slot_of(n2)) return -1;
+    return 2 * slot_of(n1) + (n1 <= W - 2 ? 1 : 0);
   }
-  __host__ __device__ static constexpr int pos0(int x) { return svdj::pos0<W>(x); }
-  __host__ __device__ static constexpr int first_pos(int a) { return slot_first_pos<W>(a); }
-  __host__ __device__ static constexpr int second_pos(int a) { return slot_second_pos<W>(a); }
-  __host__ __device__ static constexpr int first0(int a) { return a == 0 ? 2 * W - 1 : a; }
-  __host__ __device__ static constexpr int second0(int a) { return a == 0 ? 0 : 2 * W - 1 - a; }
-  __device__ static void players(int a, int st, int& p, int& q) { ring_slot<W>(a, st, p, q); }
+  // Position of player x at step 0 (inverse of players at st = 0).
+  __host__ __device__ static constexpr int pos0(int x) { return x == R ? R : (x == 0 ? R - 1 : x - 1); }
+  __host__ __device__ static constexpr int first_pos(int a) { return a == 0 ? R : a - 1; }
+  __host__ __device__ static constexpr int second_pos(int a) { return 2 * W - 2 - a; }
+  __host__ __device__ static constexpr int first0(int a) { return a == 0 ? R : a; }
+  __host__ __device__ static constexpr int second0(int a) { return a == 0 ? 0 : R - a; }
+  // Players of slot a at step st (the same movement as the DPP shifts of the
+  // register Q: firsts move right, seconds left, player N-1 fixed in slot 0):
+  // the player at ring position x after st steps is ((x - st) mod R + 1) mod R.
+  // Checked against the DPP movement by
+  // tests/test_schedule.py::test_evd_ring_matches_dpp_movement.
+  __device__ static __forceinline__ int player(int pos, int st) {
+    int x = pos - st;
+    x += x < 0 ? R : 0;
+    return x + 1 == R ? 0 : x + 1;
+  }
+  __device__ static void players(int a, int st, int& p, int& q) {
+    p = a == 0 ? R : player(a - 1, st);
+    q = player(second_pos(a), st);
+  }
   // firsts shift right, seconds shift left; slot 0's first (player 2W-1)
   // stays, slot 1 takes slot 0's second, slot W-1's second is its own first
   template <typename V>
@@ -343,7 +354,7 @@ struct Ord<W, EVD_BIP> {
   }
 };
 template <int W, int ORD>
-__host__ __device__ constexpr int block_duty_o(int a, int b) {  // 256*e + meeting, or -1
+__host__ __device__ constexpr int block_duty(int a, int b) {  // 256*e + meeting, or -1
   using O = Ord<W, ORD>;
   for (int e = 0; e < 4; ++e) {
     const int x = (e >> 1) ? O::second_pos(a) : O::first_pos(a);
@@ -394,7 +405,7 @@ struct EvdDeal {
     for (int i = 0; i < W - 1; ++i) {
       const int a = (i & 1) ? W - 2 - (i >> 1) : (i >> 1);
       for (int b = a + 1; b < W; ++b)
-        if (block_duty_o<W, ORD>(a, b) < 0) blk[g++] = (unsigned short)((a << 8) | b);
+        if (block_duty<W, ORD>(a, b) < 0) blk[g++] = (unsigned short)((a << 8) | b);
     }
     for (; g < MAXOFF * NT; ++g) blk[g] = 0xffff;
   }
@@ -412,16 +423,16 @@ constexpr bool evd_deal_ok() {
     const int a = d.blk[g] >> 8, b = d.blk[g] & 255;
     if (!(a < b && b < W) || seen[a * W + b]++) return false;
     ++dealt;
-    const int duty = block_duty_o<W, ORD>(a, b);
+    const int duty = block_duty<W, ORD>(a, b);
     if (g < W && (duty < 0 || ((duty & 255) >> 1) != g)) return false;
     if (g >= W && duty >= 0) return false;
   }
   return dealt == EvdDeal<W, NT, ORD, OPT>::NOFF;
 }
-static_assert(evd_deal_ok<32, evd_threads(32), EVD_CYCLIC>(), "EVD block dealing");
-static_assert(evd_deal_ok<64, evd_threads(64), EVD_CYCLIC>(), "EVD block dealing");
-static_assert(evd_deal_ok<32, evd_threads(32), EVD_BIP>(), "EVD block dealing");
-static_assert(evd_deal_ok<64, evd_threads(64), EVD_BIP>(), "EVD block dealing");
+static_assert(evd_deal_ok<32, kEvdThreads, EVD_CYCLIC>(), "EVD block dealing");
+static_assert(evd_deal_ok<64, kEvdThreads, EVD_CYCLIC>(), "EVD block dealing");
+static_assert(evd_deal_ok<32, kEvdThreads, EVD_BIP>(), "EVD block dealing");
+static_assert(evd_deal_ok<64, kEvdThreads, EVD_BIP>(), "EVD block dealing");
 static_assert(evd_deal_ok<64, 1024, EVD_BIP, true>(), "optimised EVD block dealing");
 static_assert(evd_deal_ok<32, 1024, EVD_BIP, true>(), "optimised EVD block dealing");
 // which dealing a kernel uses
@@ -430,12 +441,81 @@ __host__ __device__ constexpr bool evd_deal_opt() {
   return sizeof(T) == 4 && ORD == EVD_BIP && NT == 1024 && (W == 32 || W == 64);
 }
 
+// ---- pre-pass and tail shared by evd_kernel and evd_cross_kernel.
+// While a thread assembles G it folds every coupling g of columns with
+// squared norms (g_rr, g_cc) into the step's convergence value
+// max |g| / sqrt(g_rr g_cc) (columns under the floor left out, as in
+// needs_rotation) and into "does any pair pass the rotation test".
+template <typename T>
+struct AssemblyFold {
+  const T tol;
+  const int absmode;
+  const T nfloor;
+  float mx = 0.0f;
+  int need = 0;
+  __device__ __forceinline__ void add(T g, T grr, T gcc) {
+    const T d = sqrt(grr) * sqrt(gcc);
+    if (d > T(0) && (absmode || (grr > nfloor && gcc > nfloor))) {
+      const float v = (float)(fabs(g) / d);
+      mx = v > mx ? v : mx;
+    }
+    need |= needs_rotation(grr, gcc, g, tol, absmode, nfloor) ? 1 : 0;
+  }
+  // Workgroup reduce (two barriers) through the kernel's LDS words, one per
+  // wave: the convergence value into metric[0]; returns whether any thread's
+  // entries need a rotation.
+  template <int NWAVE>
+  __device__ __forceinline__ bool reduce(float (&wmax)[NWAVE], int (&wneed)[NWAVE], int& need_any,
+                                         uint32_t* metric) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    mx = wave_max(mx);
+    need = __any(need) ? 1 : 0;
+    if (lane == 0) {
+      wmax[wave] = mx;
+      wneed[wave] = need;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float m2 = 0.0f;
+      int n2 = 0;
+      for (int w = 0; w < NWAVE; ++w) {
+        m2 = wmax[w] > m2 ? wmax[w] : m2;
+        n2 |= wneed[w];
+      }
+      atomic_max_pos(&metric[0], m2);
+      need_any = n2;
+    }
+    __syncthreads();
+    return need_any != 0;
+  }
+};
+// After the steps: the second-order stop test's inputs (svdj_stop.h) from the
+// solver lanes of wave 0 -- largest effective sine into metric[4], rotation
+// count into metric[5] -- the pair's skip flag and the count of pairs that
+// rotated (metric[1]).  `any`: some inner sweep rotated.
+__device__ __forceinline__ void evd_tail(bool any, float smax, uint32_t rcount, int pair,
+                                         int32_t* skip, uint32_t* metric) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (wave == 0 && any) {
+    const float sm = wave_max(smax);
+    const uint32_t rc = wave_sum(rcount);
+    if (lane == 0) {
+      atomic_max_pos(&metric[4], sm);
+      atomicAdd(&metric[5], rc);
+    }
+  }
+  if (tid == 0) {
+    skip[pair] = any ? 0 : 1;
+    if (any) atomicAdd(&metric[1], 1u);
+  }
+}
+
 template <typename T, int W, int ORD>
-__global__ __launch_bounds__(evd_threads(W)) void evd_kernel(
+__global__ __launch_bounds__(kEvdThreads) void evd_kernel(
     const int32_t* __restrict__ pairs, int full, const T* __restrict__ slabs, int nchunk,
     T* __restrict__ D, T* __restrict__ Qout, int32_t* __restrict__ skip, T tol, int absmode,
     int max_inner, uint32_t* __restrict__ metric) {
-  constexpr int NT = evd_threads(W);
+  constexpr int NT = kEvdThreads;
   constexpr int NWAVE = NT / SVDJ_WAVE;
   constexpr int N = 2 * W;
   using O = Ord<W, ORD>;
@@ -489,90 +569,45 @@ __global__ __launch_bounds__(evd_threads(W)) void evd_kernel(
     for (int a = tid; a < N; a += NT) dg[a] = D[a < W ? bi * W + a : bj * W + (a - W)];
   }
   __syncthreads();
-  {
-    float mx = 0.0f;
-    int need = 0;
-    // store an entry at its step-0 position; fold it into the convergence
-    // value and the "anything to rotate" test
-    auto visit = [&](int r, int c, T g) {
-      Gb[0][tri_idx<N>(O::pos0(r), O::pos0(c))] = g;
-      const T grr = dg[r], gcc = dg[c];
-      const T d = sqrt(grr) * sqrt(gcc);
-      if (d > T(0) && (absmode || (grr > nfloor && gcc > nfloor))) {
-        const float v = (float)(fabs(g) / d);
-        mx = v > mx ? v : mx;
-      }
-      need |= needs_rotation(grr, gcc, g, tol, absmode, nfloor) ? 1 : 0;
-    };
-    // Slab sums with 16-byte loads, all chunks of a group in flight at once
-    // (one dependent global load per entry and chunk was ~12 us per kernel).
-    constexpr int EV = 16 / (int)sizeof(T);
-    if (full) {
-      const T* s0 = slabs + (size_t)pair * nchunk * (4 * W * W);
-      for (int gi = tid; gi < N * N / EV; gi += NT) {
-        double acc[EV];
+  // store an entry at its step-0 position; fold it into the convergence
+  // value and the "anything to rotate" test
+  AssemblyFold<T> fold{tol, absmode, nfloor};
+  auto visit = [&](int r, int c, T g) {
+    Gb[0][tri_idx<N>(O::pos0(r), O::pos0(c))] = g;
+    fold.add(g, dg[r], dg[c]);
+  };
+  // Slab sums with 16-byte loads, all chunks of a group in flight at once
+  // (one dependent global load per entry and chunk was ~12 us per kernel).
+  constexpr int EV = 16 / (int)sizeof(T);
+  if (full) {
+    const T* s0 = slabs + (size_t)pair * nchunk * (4 * W * W);
+    for (int gi = tid; gi < N * N / EV; gi += NT) {
+      const auto acc = slab_sum<SVDJ_EVD_SLAB_UNROLL>(s0, gi * EV, 4 * W * W, nchunk);
 #pragma unroll
-        for (int u = 0; u < EV; ++u) acc[u] = 0.0;
-#pragma unroll SVDJ_EVD_SLAB_UNROLL
-        for (int k = 0; k < nchunk; ++k) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(s0 + (size_t)k * 4 * W * W + gi * EV);
-          const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-          for (int u = 0; u < EV; ++u) acc[u] += (double)e[u];
-        }
-#pragma unroll
-        for (int u = 0; u < EV; ++u) {
-          const int i = gi * EV + u, r = i / N, c = i % N;
-          if (r < c) visit(r, c, (T)acc[u]);
-        }
-      }
-    } else {
-      // couplings inside a block are zero (blocks are kept internally orthogonal)
-      for (int i = tid; i < N * N; i += NT) {
-        const int r = i / N, c = i % N;
-        if (r < c && (c < W || r >= W)) Gb[0][tri_idx<N>(O::pos0(r), O::pos0(c))] = T(0);
-      }
-      const T* s0 = slabs + (size_t)pair * nchunk * (W * W);
-      for (int gi = tid; gi < W * W / EV; gi += NT) {
-        double acc[EV];
-#pragma unroll
-        for (int u = 0; u < EV; ++u) acc[u] = 0.0;
-#pragma unroll SVDJ_EVD_SLAB_UNROLL
-        for (int k = 0; k < nchunk; ++k) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(s0 + (size_t)k * W * W + gi * EV);
-          const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-          for (int u = 0; u < EV; ++u) acc[u] += (double)e[u];
-        }
-#pragma unroll
-        for (int u = 0; u < EV; ++u) {
-          const int i = gi * EV + u;
-          visit(i / W, W + i % W, (T)acc[u]);
-        }
+      for (int u = 0; u < EV; ++u) {
+        const int i = gi * EV + u, r = i / N, c = i % N;
+        if (r < c) visit(r, c, (T)acc[u]);
       }
     }
-    mx = wave_max(mx);
-    need = __any(need) ? 1 : 0;
-    if (lane == 0) {
-      wmax[wave] = mx;
-      wneed[wave] = need;
+  } else {
+    // couplings inside a block are zero (blocks are kept internally orthogonal)
+    for (int i = tid; i < N * N; i += NT) {
+      const int r = i / N, c = i % N;
+      if (r < c && (c < W || r >= W)) Gb[0][tri_idx<N>(O::pos0(r), O::pos0(c))] = T(0);
     }
-    __syncthreads();
-    if (tid == 0) {
-      float m2 = 0.0f;
-      int n2 = 0;
-      for (int w = 0; w < NWAVE; ++w) {
-        m2 = wmax[w] > m2 ? wmax[w] : m2;
-        n2 |= wneed[w];
+    const T* s0 = slabs + (size_t)pair * nchunk * (W * W);
+    for (int gi = tid; gi < W * W / EV; gi += NT) {
+      const auto acc = slab_sum<SVDJ_EVD_SLAB_UNROLL>(s0, gi * EV, W * W, nchunk);
+#pragma unroll
+      for (int u = 0; u < EV; ++u) {
+        const int i = gi * EV + u;
+        visit(i / W, W + i % W, (T)acc[u]);
       }
-      atomic_max_pos(&metric[0], m2);
-      need_any = n2;
     }
-    __syncthreads();
   }
   // If no pair passes the rotation test, the first pass would rotate nothing
   // (G never changes): it is skipped exactly.
-  const bool run = need_any != 0;
+  const bool run = fold.reduce(wmax, wneed, need_any, metric);
 
   // ---- this thread's blocks and their static addresses
   int ba[MAXOFF], bb[MAXOFF];
@@ -659,8 +694,6 @@ __global__ __launch_bounds__(evd_threads(W)) void evd_kernel(
   }
   __syncthreads();
 
-  // One block's update J^T G J (entries moved to their next-step positions)
-  // and, for a duty block, the next step's rotation of its slot.
   // One block's update J^T G J (entries moved to their next-step positions)
   // and, for a duty block, the next step's rotation of its slot.  Split in a
   // read half and a compute/write half so a thread issues the LDS reads of
@@ -773,18 +806,7 @@ __global__ __launch_bounds__(evd_threads(W)) void evd_kernel(
     while (!step(std::integral_constant<int, 0>{}) && !step(std::integral_constant<int, 1>{})) {
     }
 
-  if (wave == 0 && any) {  // second-order stop test input (metric[4], [5]; svdj_stop.h)
-    const float sm = wave_max(smax);
-    const uint32_t rc_ = wave_sum(rcount);
-    if (lane == 0) {
-      atomic_max_pos(&metric[4], sm);
-      atomicAdd(&metric[5], rc_);
-    }
-  }
-  if (tid == 0) {
-    skip[pair] = any ? 0 : 1;
-    if (any) atomicAdd(&metric[1], 1u);
-  }
+  evd_tail(any, smax, rcount, pair, skip, metric);
   // Full mode re-measured the diagonal from the data: always refresh D.
   if (!any && !full) return;
   if (any) {
@@ -873,7 +895,6 @@ __global__ __launch_bounds__((cross_threads<W, DPW>())) void evd_cross_kernel(
                 "DPW diagonals per wave >= 1");
   constexpr int N = 2 * W;
   using T2 = Pair2<T>;
-  using Q2 = Pair2<double>;
 
   __shared__ T Eb[2][W * W];  // cross couplings by (x slot, y position), double-buffered
   __shared__ T dg[N];
@@ -892,56 +913,20 @@ __global__ __launch_bounds__((cross_threads<W, DPW>())) void evd_cross_kernel(
   // summed in fp64), convergence value and the "anything to rotate" test
   for (int a = tid; a < N; a += NT) dg[a] = D[a < W ? bi * W + a : bj * W + (a - W)];
   __syncthreads();
-  {
-    float mx = 0.0f;
-    int need = 0;
-    constexpr int EV = 16 / (int)sizeof(T);
-    const T* s0 = slabs + (size_t)pair * nchunk * (W * W);
-    for (int gi = tid; gi < W * W / EV; gi += NT) {
-      double acc[EV];
+  AssemblyFold<T> fold{tol, absmode, nfloor};
+  constexpr int EV = 16 / (int)sizeof(T);
+  const T* s0 = slabs + (size_t)pair * nchunk * (W * W);
+  for (int gi = tid; gi < W * W / EV; gi += NT) {
+    const auto acc = slab_sum<SVDJ_EVD_SLAB_UNROLL>(s0, gi * EV, W * W, nchunk);
 #pragma unroll
-      for (int u = 0; u < EV; ++u) acc[u] = 0.0;
-#pragma unroll SVDJ_EVD_SLAB_UNROLL
-      for (int k = 0; k < nchunk; ++k) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(s0 + (size_t)k * W * W + gi * EV);
-        const T* e = reinterpret_cast<const T*>(&v);
-#pragma unroll
-        for (int u = 0; u < EV; ++u) acc[u] += (double)e[u];
-      }
-#pragma unroll
-      for (int u = 0; u < EV; ++u) {
-        const int i = gi * EV + u;
-        const T g = (T)acc[u];
-        Eb[0][i] = g;
-        const T grr = dg[i / W], gcc = dg[W + i % W];
-        const T d = sqrt(grr) * sqrt(gcc);
-        if (d > T(0) && (absmode || (grr > nfloor && gcc > nfloor))) {
-          const float v = (float)(fabs(g) / d);
-          mx = v > mx ? v : mx;
-        }
-        need |= needs_rotation(grr, gcc, g, tol, absmode, nfloor) ? 1 : 0;
-      }
+    for (int u = 0; u < EV; ++u) {
+      const int i = gi * EV + u;
+      const T g = (T)acc[u];
+      Eb[0][i] = g;
+      fold.add(g, dg[i / W], dg[W + i % W]);
     }
-    mx = wave_max(mx);
-    need = __any(need) ? 1 : 0;
-    if (lane == 0) {
-      wmax[wave] = mx;
-      wneed[wave] = need;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      float m2 = 0.0f;
-      int n2 = 0;
-      for (int w = 0; w < NWAVE; ++w) {
-        m2 = wmax[w] > m2 ? wmax[w] : m2;
-        n2 |= wneed[w];
-      }
-      atomic_max_pos(&metric[0], m2);
-      need_any = n2;
-    }
-    __syncthreads();
   }
-  const bool run = need_any != 0 && (ABL & 16) == 0;
+  const bool run = fold.reduce(wmax, wneed, need_any, metric) && (ABL & 16) == 0;
   const int inner = max_inner < kCrossMaxInner ? max_inner : kCrossMaxInner;
 
   // ---- LDS groups of waves >= 1: (i, d), d = DPW (w - 1) + 3 + j (W = 64:
@@ -1095,19 +1080,8 @@ __global__ __launch_bounds__((cross_threads<W, DPW>())) void evd_cross_kernel(
     while (!step(std::integral_constant<int, 0>{}) && !step(std::integral_constant<int, 1>{})) {
     }
 
-  if (wave == 0 && any) {  // second-order stop test input (metric[4], [5]; svdj_stop.h)
-    const float sm = wave_max(smax);
-    const uint32_t rc_ = wave_sum(rcount);
-    if (lane == 0) {
-      atomic_max_pos(&metric[4], sm);
-      atomicAdd(&metric[5], rc_);
-    }
-  }
-  if (tid == 0) {
-    skip[pair] = any ? 0 : 1;
-    nsteps[pair] = gs;
-    if (any) atomicAdd(&metric[1], 1u);
-  }
+  evd_tail(any, smax, rcount, pair, skip, metric);
+  if (tid == 0) nsteps[pair] = gs;
   if (any && solver) {  // diagonals after the last executed step (gs - 1)
     D[bi * W + a] = dx_out;
     D[bj * W + ((a + gs - 1) & (W - 1))] = dy_out;
@@ -1140,6 +1114,38 @@ __device__ __forceinline__ Pair2<double> rotation_cs(double t) {
   const double c = 1.0 / sqrt(fma(t, t, 1.0));
   return Pair2<double>{c, t * c};
 }
+// The rotation loop of the Q builds (qbuild_kernel, qbuild_quad_kernel): the
+// ns recorded steps of one pair (tangents at rp, W per step) applied to this
+// lane's R rows of the columns of slot a -- qx[i] the x column, qy[i] the y
+// column at position a.  NT threads stage kQbChunk steps at a time in rs as
+// fp64 (c, s); every thread of the workgroup calls it (barriers).
+template <int W, int R, int NT, typename T>
+__device__ __forceinline__ void qbuild_rotate(const T* rp, int ns, Pair2<double> (&rs)[kQbChunk * W],
+                                              int a, double (&qx)[R], double (&qy)[R]) {
+  using Q2 = Pair2<double>;
+  // One chunk as a lambda: written straight into the chunk loop, the compiler
+  // waited for the look-ahead read of step t + 2 right after issuing it in
+  // most instantiations (profiles/evd_shared, read from the assembly).
+  auto chunk = [&](int t0) {
+    const int nc = ns - t0 < kQbChunk ? ns - t0 : kQbChunk;
+    for (int i = threadIdx.x; i < nc * W; i += NT) rs[i] = rotation_cs(rp[(size_t)t0 * W + i]);
+    __syncthreads();
+    Q2 n0 = rs[a], n1 = nc > 1 ? rs[W + a] : Q2{1.0, 0.0};
+    for (int t = 0; t < nc; ++t) {
+      const Q2 cs = n0;
+      n0 = n1;
+      if (t + 2 < nc) n1 = rs[(t + 2) * W + a];
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const double x = qx[i], y = qy[i];
+        qx[i] = cs.x * x - cs.y * y;
+        qy[i] = bip_shift<W>(cs.y * x + cs.x * y, a);
+      }
+    }
+    __syncthreads();  // the next chunk overwrites rs
+  };
+  for (int t0 = 0; t0 < ns; t0 += kQbChunk) chunk(t0);
+}
 template <int W, int R>
 __host__ __device__ constexpr int qbuild_blocks() {  // workgroups per pair
   return (2 * W) / (R * (SVDJ_WAVE / W) * (kQbThreads / SVDJ_WAVE));
@@ -1166,24 +1172,7 @@ __global__ __launch_bounds__(kQbThreads) void qbuild_kernel(
     qx[i] = (k0 + i == a) ? 1.0 : 0.0;
     qy[i] = (k0 + i == W + a) ? 1.0 : 0.0;
   }
-  for (int t0 = 0; t0 < ns; t0 += kQbChunk) {
-    const int nc = ns - t0 < kQbChunk ? ns - t0 : kQbChunk;
-    for (int i = threadIdx.x; i < nc * W; i += kQbThreads) rs[i] = rotation_cs(rp[(size_t)t0 * W + i]);
-    __syncthreads();
-    Q2 n0 = rs[a], n1 = nc > 1 ? rs[W + a] : Q2{1.0, 0.0};
-    for (int t = 0; t < nc; ++t) {
-      const Q2 cs = n0;
-      n0 = n1;
-      if (t + 2 < nc) n1 = rs[(t + 2) * W + a];
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const double x = qx[i], y = qy[i];
-        qx[i] = cs.x * x - cs.y * y;
-        qy[i] = bip_shift<W>(cs.y * x + cs.x * y, a);
-      }
-    }
-    __syncthreads();  // the next chunk overwrites rs
-  }
+  qbuild_rotate<W, R, kQbThreads>(rp, ns, rs, a, qx, qy);
   T* qo = Qall + (size_t)pair * N * N;
   const int yc = W + (a + ns) % W;
 #pragma unroll

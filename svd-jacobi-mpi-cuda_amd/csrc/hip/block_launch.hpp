@@ -258,11 +258,11 @@ static int launch_evd(const Chain<T>& c, int s) {
       hipLaunchKernelGGL((qbuild_kernel<T, W, 4>), dim3(c.P, qbuild_blocks<W, 4>()),
                          dim3(kQbThreads), 0, c.st, c.rec, c.nsteps, c.skipb[b], c.Qb[b]);
   } else if (mode == SVDJ_STEP_CROSS_BIP)
-    hipLaunchKernelGGL((evd_kernel<T, W, EVD_BIP>), dim3(c.P), dim3(evd_threads(W)), 0, c.st, pr,
+    hipLaunchKernelGGL((evd_kernel<T, W, EVD_BIP>), dim3(c.P), dim3(kEvdThreads), 0, c.st, pr,
                        0, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol, c.tol_mode,
                        c.max_inner, c.metric);
   else
-    hipLaunchKernelGGL((evd_kernel<T, W, EVD_CYCLIC>), dim3(c.P), dim3(evd_threads(W)), 0, c.st,
+    hipLaunchKernelGGL((evd_kernel<T, W, EVD_CYCLIC>), dim3(c.P), dim3(kEvdThreads), 0, c.st,
                        pr, full, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol,
                        c.tol_mode, c.max_inner, c.metric);
   SVDJ_LAUNCH_CHECK();

@@ -1,6 +1,6 @@
 // Quad step of the block Jacobi sweep (block.hip): two consecutive cross
 // steps fused (fp32, W = 64, split-bf16 apply) -- the Q builds, the Gram-space
-// update, the T-stationary apply, the slab sums and the six-Gram kernel.
+// update, the T-stationary apply and the six-Gram kernel.
 // The stage comment is at "quad step" below.
 #pragma once
 #include "block_apply.hpp"
@@ -91,24 +91,7 @@ __global__ __launch_bounds__(NT) void qbuild_quad_kernel(
       qy[i] = (rb & 1) != j ? ty[(size_t)kl * N + W + a] : 0.0;
     }
   }
-  for (int t0 = 0; t0 < ns; t0 += kQbChunk) {
-    const int nc = ns - t0 < kQbChunk ? ns - t0 : kQbChunk;
-    for (int i = threadIdx.x; i < nc * W; i += NT) rs[i] = rotation_cs(rp[(size_t)t0 * W + i]);
-    __syncthreads();
-    Q2 n0 = rs[a], n1 = nc > 1 ? rs[W + a] : Q2{1.0, 0.0};
-    for (int t = 0; t < nc; ++t) {
-      const Q2 cs = n0;
-      n0 = n1;
-      if (t + 2 < nc) n1 = rs[(t + 2) * W + a];
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const double x = qx[i], y = qy[i];
-        qx[i] = cs.x * x - cs.y * y;
-        qy[i] = bip_shift<W>(cs.y * x + cs.x * y, a);
-      }
-    }
-    __syncthreads();
-  }
+  qbuild_rotate<W, R, NT>(rp, ns, rs, a, qx, qy);
   const int yr = (a + ns) & (W - 1);
   if constexpr (PHASE == 1) {
     double* qo = T1 + (size_t)pair * N * N;
@@ -191,21 +174,12 @@ __global__ __launch_bounds__(NT) void quad_update_kernel(
   // (16-byte loads, four independent sums per thread and four slabs' worth in
   // flight: the one-float loop was load-latency bound, 94 us per 128-pair quad
   // step at 83 % wait-any, profiles/r5_prof)
-  const float4* base = reinterpret_cast<const float4*>(slabs + (size_t)q * 4 * gch * W * W);
+  const float* base = slabs + (size_t)q * 4 * gch * W * W;
   constexpr int E4 = W * W / 4;
 #pragma unroll 4
   for (int idx = tid; idx < 4 * E4; idx += kUpdThreads) {
     const int r = idx / E4, e4 = idx % E4, i = (4 * e4) / W, jj = (4 * e4) % W;
-    const float4* p = base + (size_t)r * gch * E4 + e4;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int k = 0; k < gch; ++k) {
-      const float4 v = p[(size_t)k * E4];
-      s0 += (double)v.x;
-      s1 += (double)v.y;
-      s2 += (double)v.z;
-      s3 += (double)v.w;
-    }
-    const double sv[4] = {s0, s1, s2, s3};
+    const auto sv = slab_sum<0>(base + (size_t)r * gch * W * W, 4 * e4, W * W, gch);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int ju = jj + u;
@@ -742,31 +716,6 @@ apply_quad_ts_kernel(float* __restrict__ A, int lda, int a_tiles, float* __restr
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
-}
-
-// The quad step's Grams summed over their row chunks, spread over 4 x 3P
-// workgroups: fp64 sums in chunk order rounded once -- bitwise what
-// evd_cross_kernel and quad_update_kernel compute from the chunks -- so that
-// with many chunks (few quads: 64 at 4 quads) the latency-bound consumers,
-// one workgroup per pair, read one slab instead of all chunks (8-GPU plan:
-// quad_update 334 us per launch reading 64 chunks, profiles/r5_quad2).
-constexpr int kRedThreads = 256;
-__global__ __launch_bounds__(kRedThreads) void slab_reduce_kernel(const float* __restrict__ in,
-                                                                  int gch, float* __restrict__ out) {
-  constexpr int W = 64, E4 = W * W / 4;
-  const int slab = blockIdx.x, e4 = blockIdx.y * kRedThreads + threadIdx.x;
-  const float4* p = reinterpret_cast<const float4*>(in) + (size_t)slab * gch * E4 + e4;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll 8
-  for (int k = 0; k < gch; ++k) {
-    const float4 v = p[(size_t)k * E4];
-    s0 += (double)v.x;
-    s1 += (double)v.y;
-    s2 += (double)v.z;
-    s3 += (double)v.w;
-  }
-  reinterpret_cast<float4*>(out)[(size_t)slab * E4 + e4] =
-      make_float4((float)s0, (float)s1, (float)s2, (float)s3);
 }
 
 // The six cross Grams of a quad step, every block read ONCE (round 5).  The

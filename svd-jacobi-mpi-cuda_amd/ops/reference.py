@@ -76,7 +76,7 @@ def round_robin_pairs(N):
 
 def ring_pairs(N):
     """The cyclic ordering as evd_kernel steps through it (block_evd.hpp
-    ring_slot): at step st slot a pairs player N-1 (a = 0) or the player at
+    Ord<W, EVD_CYCLIC>::players): at step st slot a pairs player N-1 (a = 0) or the player at
     ring position a-1 with the one at position N-2-a; the player at position x
     after st steps is ((x - st) mod (N-1) + 1) mod (N-1).  The same pairs per
     sweep as round_robin_pairs, in another order of steps."""

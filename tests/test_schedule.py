@@ -131,7 +131,7 @@ def test_distributed_sweep_covers_every_block_pair_once(P, k):
 
 
 def test_evd_ring_matches_dpp_movement():
-    """The EVD kernel computes slot players arithmetically (ring_slot in
+    """The EVD kernel computes slot players arithmetically (Ord<W, EVD_CYCLIC>::players in
     csrc/hip/block_evd.hpp) for the G updates, while the register Q follows the
     DPP shifts; both must describe the same circle-method movement and cover
     every pair once per N-1 steps."""
@@ -175,7 +175,7 @@ def _pos_next(W, P):
 
 
 def _next_meeting(W, P1, P2):
-    """Python twin of block_evd.hpp next_meeting (position R = fixed player)."""
+    """Python twin of block_evd.hpp Ord<W, EVD_CYCLIC>::next_meeting (position R = fixed player)."""
     R = 2 * W - 1
 
     def slot_of(pos):

@@ -56,7 +56,7 @@ int main(int argc, char** argv) {
   auto reset = [&]() { (void)hipMemcpy(dD, hd.data(), hd.size() * 4, hipMemcpyHostToDevice); };
   reset();
   const double tb = time_it([&]() {
-    hipLaunchKernelGGL((svdj::evd_kernel<float, W, svdj::EVD_BIP>), dim3(P), dim3(svdj::evd_threads(W)), 0,
+    hipLaunchKernelGGL((svdj::evd_kernel<float, W, svdj::EVD_BIP>), dim3(P), dim3(svdj::kEvdThreads), 0,
                        nullptr, dp, 0, dsl, nchunk, dD, dQ, dsk, 1e-6f, 0, 1, dm);
   }, reps);
   reset();
