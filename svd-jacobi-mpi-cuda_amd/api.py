@@ -86,7 +86,11 @@ def svd_batched(A: torch.Tensor, jobu=SVDOptions.AllVec, jobv=SVDOptions.AllVec,
     On a GPU, matrices with at most 64 columns (after a wide input is
     transposed) that fit in a CU's LDS are solved by one launch, one
     workgroup per matrix (models/batched.py); anything else, and CPU input,
-    runs :func:`svd` per matrix.  ``device``, ``config`` and the keyword
+    runs :func:`svd` per matrix.  ``batched="block"`` asks for the stacked
+    block engine instead (any column count, either device: the whole batch
+    through the block path's step kernels, every matrix with its own stop
+    test; ``block`` sets W, ``extra={"batch_chunk": c}`` the matrices per
+    chunk); it is never chosen by default.  ``device``, ``config`` and the keyword
     overrides are those of :func:`svd` (``tol``, ``max_sweeps``, ``sort``,
     ``tol_mode``, ``dtype``).  Returns a :class:`BatchedSVDResult` that
     unpacks as ``U, S, V`` with shapes (..., m, k), (..., k), (..., n, k)."""

@@ -76,6 +76,10 @@ class SolverConfig:
     # + Jacobi on R + U = Q U_R 1.99 s (Householder QR via rocSOLVER geqrf: 5.4 s).
     qr_ratio: float = 2.0
     panel_rows: int = 0             # svd_batched, precondition="qr": rows per QR panel (0: auto)
+    # svd_batched: auto (the LDS-resident kernels up to 64 columns, else svd() per matrix) |
+    # block (the whole batch stacked into the block path's step kernels, any column count;
+    # models/batched.py; extra["batch_chunk"]: matrices per chunk, within the byte cap)
+    batched: str = "auto"
     chains: int = 2                 # block path: independent step chains on separate streams
     num_threads: int = 0            # CPU oracle OpenMP threads (0: default)
     progress: bool = False          # rank 0 prints one line per sweep to stderr
@@ -108,6 +112,8 @@ class SolverConfig:
             raise ValueError(f"exchange must be auto, direct or spread, got {self.exchange!r}")
         if self.quad not in ("auto", "on", "off"):
             raise ValueError(f"quad must be auto, on or off, got {self.quad!r}")
+        if self.batched not in ("auto", "block"):
+            raise ValueError(f"batched must be auto or block, got {self.batched!r}")
         if self.stop_rule not in ("second_order", "no_rotation"):
             raise ValueError(f"stop_rule must be second_order or no_rotation, "
                              f"got {self.stop_rule!r}")

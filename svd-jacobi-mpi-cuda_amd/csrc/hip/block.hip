@@ -78,11 +78,11 @@ static int check_dims(int m_pad, int lda, const void* V, int n_v, int ldv, int m
   return 0;
 }
 
-extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,
-                                int ldv, void* D, const int32_t* pairs, int P, int steps,
-                                const int32_t* modes, double tol, int tol_mode, int max_inner,
-                                void* ws, size_t ws_bytes, uint32_t* metric, int mma,
-                                void* stream) {
+extern "C" int svdj_block_steps_grouped(int dtype, int W, int m_pad, void* A, int lda, void* V,
+                                        int n_v, int ldv, void* D, const int32_t* pairs, int P,
+                                        int steps, const int32_t* modes, double tol, int tol_mode,
+                                        int max_inner, void* ws, size_t ws_bytes, uint32_t* metric,
+                                        int group_blocks, int mma, void* stream) {
   // mma: the apply's matrix-core mode | SVDJ_STEPS_* (svdj_hip.h; chain_init)
   int rc = check_dims(m_pad, lda, V, n_v, ldv, mma & SVDJ_MMA_MASK);
   if (rc) return rc;
@@ -97,9 +97,18 @@ extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, v
     Chain<T> c;
     const int err = chain_init<T, W_>(c, m_pad, (T*)A, lda, (T*)V, n_v, ldv, (T*)D, pairs, P,
                                       steps, modes, tol, tol_mode, max_inner, ws, ws_bytes, metric,
-                                      mma, (hipStream_t)stream);
+                                      mma, (hipStream_t)stream, group_blocks);
     return err ? err : block_steps_t<T, W_>(c);
   });
+}
+
+extern "C" int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,
+                                int ldv, void* D, const int32_t* pairs, int P, int steps,
+                                const int32_t* modes, double tol, int tol_mode, int max_inner,
+                                void* ws, size_t ws_bytes, uint32_t* metric, int mma,
+                                void* stream) {
+  return svdj_block_steps_grouped(dtype, W, m_pad, A, lda, V, n_v, ldv, D, pairs, P, steps, modes,
+                                  tol, tol_mode, max_inner, ws, ws_bytes, metric, 0, mma, stream);
 }
 
 extern "C" int svdj_block_solve(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,

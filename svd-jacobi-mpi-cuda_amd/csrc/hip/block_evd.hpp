@@ -7,6 +7,7 @@
 #pragma once
 #include "common.hpp"
 #include "evd_deal_tables.hpp"
+#include "svdj_stop.h"
 
 namespace svdj {
 
@@ -151,7 +152,23 @@ __device__ __forceinline__ bool needs_rotation(double gpp, double gqq, double gp
 template <typename T>
 __device__ __forceinline__ float eff_sine(T s, T dp, T dq) {
   if (s == T(0)) return 0.0f;
-  const float a = (float)fabs(dp), b = (float)fabs(dq);
+  T pa = fabs(dp), pb = fabs(dq);
+  if constexpr (sizeof(T) == 8) {
+    // fp64 squared norms may lie outside float's range (a matrix scaled by
+    // 2^200: the ratio became inf * 0 = NaN, atomic_max_pos dropped it, and
+    // the second-order rule saw ms = 0 and stopped the solve after one sweep).
+    // Bring the larger one to [0.5, 1) by a power of two first.  The scaling
+    // itself is exact; a pair whose two squared norms were both normal floats
+    // gives the value it gave as long as the smaller one stays a normal float
+    // after the scaling, i.e. for ratios up to about 2^125.  Beyond that the
+    // smaller one flushes to 0 and the result is the 1.0f cap below, where the
+    // unscaled form gave a huge finite value or inf: either keeps the
+    // second-order rule from firing.
+    const int e = __builtin_amdgcn_frexp_exp(pa > pb ? pa : pb);
+    pa = ldexp(pa, -e);
+    pb = ldexp(pb, -e);
+  }
+  const float a = (float)pa, b = (float)pb;
   const float lo = fminf(a, b), hi = fmaxf(a, b);
   return lo > 0.0f ? fabsf((float)s) * __builtin_amdgcn_sqrtf(hi * __builtin_amdgcn_rcpf(lo)) : 1.0f;
 }
@@ -514,7 +531,7 @@ template <typename T, int W, int ORD>
 __global__ __launch_bounds__(kEvdThreads) void evd_kernel(
     const int32_t* __restrict__ pairs, int full, const T* __restrict__ slabs, int nchunk,
     T* __restrict__ D, T* __restrict__ Qout, int32_t* __restrict__ skip, T tol, int absmode,
-    int max_inner, uint32_t* __restrict__ metric) {
+    int max_inner, uint32_t* __restrict__ metric, int group_blocks = 0) {
   constexpr int NT = kEvdThreads;
   constexpr int NWAVE = NT / SVDJ_WAVE;
   constexpr int N = 2 * W;
@@ -554,6 +571,8 @@ __global__ __launch_bounds__(kEvdThreads) void evd_kernel(
   const int pair = blockIdx.x;
   const int bi = pairs[2 * pair], bj = pairs[2 * pair + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // grouped metrics (svdj_block_steps_grouped): the pair's matrix has its own words
+  metric += group_blocks ? (bi / group_blocks) * SVDJ_METRIC_WORDS : 0;
   const T nfloor = norm_floor<T>(metric);
 
   // ---- assemble G: diagonal first (player order), then every off-diagonal
@@ -886,7 +905,8 @@ template <typename T, int W, int ABL = 0, int DPW = 2>
 __global__ __launch_bounds__((cross_threads<W, DPW>())) void evd_cross_kernel(
     const int32_t* __restrict__ pairs, const T* __restrict__ slabs, int nchunk,
     T* __restrict__ D, T* __restrict__ rec, int32_t* __restrict__ nsteps,
-    int32_t* __restrict__ skip, T tol, int absmode, int max_inner, uint32_t* __restrict__ metric) {
+    int32_t* __restrict__ skip, T tol, int absmode, int max_inner, uint32_t* __restrict__ metric,
+    int group_blocks = 0) {
   static_assert(W == 32 || W == 64, "cross EVD: W = 32 or 64");
   static_assert(W == 64 || DPW == 2, "W = 32: two diagonals per wave (one per lane half)");
   constexpr int NT = cross_threads<W, DPW>();
@@ -907,6 +927,8 @@ __global__ __launch_bounds__((cross_threads<W, DPW>())) void evd_cross_kernel(
   const int pair = blockIdx.x;
   const int bi = pairs[2 * pair], bj = pairs[2 * pair + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // grouped metrics (svdj_block_steps_grouped): the pair's matrix has its own words
+  metric += group_blocks ? (bi / group_blocks) * SVDJ_METRIC_WORDS : 0;
   const T nfloor = norm_floor<T>(metric);
 
   // ---- assemble: diagonals from D, E_0[i][p] = C[i][p] (split-K slabs

@@ -25,9 +25,17 @@ template <typename T, int W>
 static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int ldv, T* D,
                       const int32_t* pairs, int P, int steps, const int32_t* modes, double tol,
                       int tol_mode, int max_inner, void* ws, size_t ws_bytes, uint32_t* metric,
-                      int flags, hipStream_t st) {
+                      int flags, hipStream_t st, int group_blocks = 0) {
   const int mma = flags & SVDJ_MMA_MASK;
   const bool quad = has_quad_steps(modes, steps);
+  if (group_blocks < 0) {
+    set_error("group_blocks %d must be >= 0", group_blocks);
+    return -2;
+  }
+  if (group_blocks && quad) {  // the quad kernels keep one metric
+    set_error("quad steps are not part of the grouped path (group_blocks %d)", group_blocks);
+    return -2;
+  }
   if (quad && !has_quad(sizeof(T), W)) {
     set_error("quad steps need fp32 data and W = 64");
     return -3;
@@ -49,6 +57,7 @@ static int chain_init(Chain<T>& c, int m_pad, T* A, int lda, T* V, int n_v, int 
   c.m_pad = m_pad; c.lda = lda; c.n_v = n_v; c.ldv = ldv; c.P = P; c.steps = steps;
   c.A = A; c.V = V; c.D = D; c.pairs = pairs; c.modes = modes; c.st = st;
   c.tol = tol; c.tol_mode = tol_mode; c.max_inner = max_inner; c.metric = metric; c.mma = mma;
+  c.group_blocks = group_blocks;
   c.gram_np = (flags & SVDJ_STEPS_GRAM2) ? 2 : 3;
   c.shared = (flags & SVDJ_STEPS_SHARED_GPU) != 0;
   c.g = make_geometry(W, P, m_pad, V ? n_v : 0, mma);
@@ -239,7 +248,7 @@ static int launch_evd(const Chain<T>& c, int s) {
     }
     hipLaunchKernelGGL((evd_cross_kernel<T, W>), dim3(c.P), dim3(cross_threads<W>()), 0, c.st, pr,
                        gs, gn, c.D, c.rec, c.nsteps, c.skipb[b], (T)c.tol, c.tol_mode, c.max_inner,
-                       c.metric);
+                       c.metric, c.group_blocks);
     SVDJ_LAUNCH_CHECK();
     constexpr int RL = W == 64 ? 16 : 8;  // one workgroup per pair
     // 16 rows per lane from 64 pairs per step; at 32 pairs 4 rows per lane is
@@ -260,11 +269,11 @@ static int launch_evd(const Chain<T>& c, int s) {
   } else if (mode == SVDJ_STEP_CROSS_BIP)
     hipLaunchKernelGGL((evd_kernel<T, W, EVD_BIP>), dim3(c.P), dim3(kEvdThreads), 0, c.st, pr,
                        0, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol, c.tol_mode,
-                       c.max_inner, c.metric);
+                       c.max_inner, c.metric, c.group_blocks);
   else
     hipLaunchKernelGGL((evd_kernel<T, W, EVD_CYCLIC>), dim3(c.P), dim3(kEvdThreads), 0, c.st,
                        pr, full, c.slabs, c.g.gchunks, c.D, c.Qb[b], c.skipb[b], (T)c.tol,
-                       c.tol_mode, c.max_inner, c.metric);
+                       c.tol_mode, c.max_inner, c.metric, c.group_blocks);
   SVDJ_LAUNCH_CHECK();
   return 0;
 }

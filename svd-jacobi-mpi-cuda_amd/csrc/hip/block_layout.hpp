@@ -115,6 +115,9 @@ struct Chain {
   double tol;  // the EVDs' rotation threshold, relative or (tol_mode 1) absolute
   int tol_mode, max_inner;
   uint32_t* metric;  // svdj_stop.h
+  // 0: one metric.  g > 0: metric is uint32[groups][SVDJ_METRIC_WORDS] and a
+  // pair (bi, bj) accumulates into group bi / g (svdj_block_steps_grouped)
+  int group_blocks;
   int mma;  // the apply's matrix-core mode (SVDJ_MMA_*)
   int gram_np;  // bf16 parts of the quad Gram (3; 2: SVDJ_STEPS_GRAM2)
   int shared;  // another chain runs concurrently on this GPU (SVDJ_STEPS_SHARED_GPU)

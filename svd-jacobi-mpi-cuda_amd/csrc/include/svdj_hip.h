@@ -136,6 +136,19 @@ int svdj_block_steps(int dtype, int W, int m_pad, void* A, int lda, void* V,
                      int steps, const int32_t* modes, double tol, int tol_mode,
                      int max_inner_sweeps, void* workspace, size_t ws_bytes,
                      uint32_t* metric, int mma, void* stream);
+// svdj_block_steps with one metric per group of blocks: metric is device
+// uint32[groups][SVDJ_METRIC_WORDS], and a pair (bi, bj) reads the floor of and
+// accumulates into group bi / group_blocks (group_blocks > 0; both blocks of a
+// pair must lie in one group).  With B matrices stacked side by side as column
+// blocks of one array, k blocks each, group_blocks = k makes a step whose pair
+// list never crosses a matrix B independent block-Jacobi steps in one launch,
+// each with its own stop-test words.  group_blocks = 0 is svdj_block_steps.
+// Quad modes are refused (-2) when group_blocks != 0.
+int svdj_block_steps_grouped(int dtype, int W, int m_pad, void* A, int lda, void* V, int n_v,
+                             int ldv, void* D, const int32_t* pairs, int P, int steps,
+                             const int32_t* modes, double tol, int tol_mode,
+                             int max_inner_sweeps, void* workspace, size_t ws_bytes,
+                             uint32_t* metric, int group_blocks, int mma, void* stream);
 
 // Single-GPU block solve: round-robin over nb = ncols/W blocks (nb even),
 // first step of every sweep SVDJ_STEP_FULL; inner_order (SVDJ_INNER_*) gives
@@ -307,6 +320,39 @@ int svdj_batched_tall_svd(int dtype, int batch, int m, int n, const void* A, lon
                           long sc, void* U, void* S, void* V, void* tau_ws, int panel_rows,
                           double tol, int tol_mode, int max_sweeps, int32_t* sweeps, float* off,
                           void* stream);
+
+// ---------------------------------------------------------------------------
+// Batched path for matrices wider than 64 columns (csrc/hip/batched_block.hip):
+// the pack and finalize passes around svdj_block_steps_grouped.  `batch`
+// matrices (m x n, m >= n >= 1) are stacked side by side in one column-major
+// image At of m_pad rows (a multiple of SVDJ_ROW_ALIGN, >= m) and batch x
+// ncols columns (ncols a multiple of 64, >= n): matrix b's column j is stacked
+// column b ncols + j; pad rows and columns are zero.  The stacked V has n_v
+// rows (a multiple of SVDJ_ROW_ALIGN, >= ncols).  At most 65535 matrices and
+// 2^31 - 1 stacked columns per call.
+//
+// Pack: reads A once through element strides (sb, sr, sc) as svdj_batched_svd
+// does (coalesced when sc or sr is 1) and writes
+//   At      the stacked image
+//   V       NULL, or the stacked V: an identity block per matrix
+//   D       [batch ncols], data type: squared column norms, fp64 accumulation
+//   metric  uint32[batch][SVDJ_METRIC_WORDS]: matrix b's underflow floor
+//           max(m_pad realmin, m_pad realmin / eps * its largest D) in words
+//           2..3 of its group, every other word zero
+// Returns 0; -2 with the error string set and nothing launched on a bad
+// argument; batch == 0 returns 0 without any HIP call.
+int svdj_stack_pack(int dtype, int batch, int m, int n, const void* A, long sb, long sr, long sc,
+                    int m_pad, int ncols, void* At, int lda, void* V, int n_v, int ldv, void* D,
+                    uint32_t* metric, void* stream);
+// Finalize: reads the stacked images once and writes
+//   S       contiguous (batch, n): sigma = the fp64 column norm
+//   U       NULL, or contiguous (batch, m, n) row-major: the columns of At,
+//           divided by sigma when scale_u (a sigma == 0 column is left as it is)
+//   Vout    NULL, or contiguous (batch, n, n) row-major from the stacked V
+// Returns as svdj_stack_pack.
+int svdj_stack_finalize(int dtype, int batch, int m, int n, int m_pad, int ncols, const void* At,
+                        int lda, const void* V, int n_v, int ldv, void* U, void* S, void* Vout,
+                        int scale_u, void* stream);
 
 // ---------------------------------------------------------------------------
 // Post-processing / utilities.

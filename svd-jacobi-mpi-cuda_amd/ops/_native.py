@@ -117,6 +117,16 @@ def hip_lib():
              [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
               c_int, c_int, c_i32_p, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int,
               c_void_p])
+        _sig(lib, "svdj_block_steps_grouped", c_int,
+             [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+              c_int, c_int, c_i32_p, c_double, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int,
+              c_int, c_void_p])
+        _sig(lib, "svdj_stack_pack", c_int,
+             [c_int, c_int, c_int, c_int, c_void_p, C.c_long, C.c_long, C.c_long, c_int, c_int,
+              c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p])
+        _sig(lib, "svdj_stack_finalize", c_int,
+             [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+              c_void_p, c_void_p, c_void_p, c_int, c_void_p])
         _sig(lib, "svdj_block_solve", c_int,
              [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
               c_double, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_f64_p, c_int,

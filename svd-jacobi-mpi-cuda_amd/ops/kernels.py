@@ -83,16 +83,19 @@ def _check_layout(At: torch.Tensor, m_pad: int):
 METRIC_WORDS = 8  # csrc/include/svdj_stop.h SVDJ_METRIC_WORDS
 
 
-def new_metric(device) -> torch.Tensor:
+def new_metric(device, groups: int | None = None) -> torch.Tensor:
     """Per-sweep stop-test state: [0] max convergence value, [1] rotated
     pairs, the negligible-column floor of the solve (block path), and for the
     block path's second-order stop test the largest effective sine of an
     applied rotation and the number of column rotations applied.  Device:
     int32[8] (csrc/include/svdj_stop.h: floor a double in [2..3], sine float
-    bits in [4], count [5]); CPU: float64[5] (floor [2], sine [3], count [4])."""
+    bits in [4], count [5]); CPU: float64[5] (floor [2], sine [3], count [4]).
+    ``groups``: one such row per group, (groups, 8) or (groups, 5), for
+    :func:`block_steps` with ``group_blocks``."""
+    shape = () if groups is None else (int(groups),)
     if torch.device(device).type == "cpu":
-        return torch.zeros(5, dtype=torch.float64)
-    return torch.zeros(METRIC_WORDS, dtype=torch.int32, device=device)
+        return torch.zeros(*shape, 5, dtype=torch.float64)
+    return torch.zeros(*shape, METRIC_WORDS, dtype=torch.int32, device=device)
 
 
 def reset_metric(metric: torch.Tensor):
@@ -168,6 +171,27 @@ def read_stop(metric: torch.Tensor):
     rotations) -- synchronises."""
     v = metric_stop_values(metric).cpu()
     return float(v[0]), float(v[1]), int(v[2]), int(v[3])
+
+
+def reset_group_metrics(metric: torch.Tensor, groups: torch.Tensor):
+    """:func:`reset_metric` on the rows ``groups`` (an index tensor on the
+    metric's device) of a grouped metric."""
+    last = 3 if metric.device.type == "cpu" else 4
+    metric[groups, :2] = 0
+    metric[groups, last:] = 0
+
+
+def read_group_stops(metric: torch.Tensor):
+    """A grouped metric's stop-test inputs on the host: float64 arrays (groups,)
+    of the largest convergence value, the largest effective sine, the rotated
+    pairs and the column rotations -- one copy, synchronises."""
+    if metric.device.type == "cpu":
+        h = metric.numpy()
+        return h[:, 0].copy(), h[:, 3].copy(), h[:, 1].copy(), h[:, 4].copy()
+    h = np.ascontiguousarray(metric.cpu().numpy())
+    f, u = h.view(np.float32), h.view(np.uint32)
+    return (f[:, 0].astype(np.float64), f[:, 4].astype(np.float64), u[:, 1].astype(np.float64),
+            u[:, 5].astype(np.float64))
 
 
 STOP_RULES = {"no_rotation": 0, "second_order": 1}
@@ -322,7 +346,8 @@ def check_block(dtype, W):
 
 def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_slot: int = 0,
                 mma="native", pool: dict | None = None, tol_mode="relative",
-                inner_order="cyclic", gram_parts: int = 3, shared_gpu: bool = False):
+                inner_order="cyclic", gram_parts: int = 3, shared_gpu: bool = False,
+                group_blocks: int | None = None, ws: torch.Tensor | None = None):
     """Run ``len(modes)`` block steps on the current stream.  pairs: int32
     (steps, P, 2) on At's device (block indices local to At); modes: list of
     STEP_* codes (see step_modes for ``inner_order``).  Chains running
@@ -330,25 +355,53 @@ def block_steps(At, Vt, D, m_pad, pairs, W, modes, tol, max_inner, metric, ws_sl
     ``gram_parts`` 2: the quad Gram on 2 bf16 parts (STEPS_GRAM2; GPU only,
     the CPU emulation keeps the exact Gram).  ``shared_gpu``: another chain
     runs concurrently on this GPU (STEPS_SHARED_GPU: the quad apply leaves it
-    a quarter of the CUs)."""
+    a quarter of the CUs).  ``group_blocks`` (svdj_block_steps_grouped): g > 0
+    -- ``metric`` is :func:`new_metric` with ``groups`` rows and a pair (bi,
+    bj) reads the floor of and accumulates into row bi // g; no quad steps;
+    0 -- one metric through the grouped entry; None -- svdj_block_steps.
+    ``ws``: the caller's workspace (uint8, at least svdj_block_workspace_bytes)
+    instead of the cached one."""
     modes = step_modes(modes, inner_order)
     _check_layout(At, m_pad)
     check_block(At.dtype, W)
     steps, P = int(pairs.shape[0]), int(pairs.shape[1])
+    if group_blocks is not None and (group_blocks < 0 or (
+            group_blocks and (STEP_QUAD in modes or STEP_QUAD_SECOND in modes))):
+        raise ValueError(f"group_blocks={group_blocks}: must be >= 0, and no quad steps")
     if steps == 0 or P == 0:
         return
     if At.is_cuda:
-        ws = block_workspace(At.dtype, W, P, m_pad, At.device, ws_slot, pool,
-                             quad=STEP_QUAD in modes)
+        if ws is None:
+            ws = block_workspace(At.dtype, W, P, m_pad, At.device, ws_slot, pool,
+                                 quad=STEP_QUAD in modes)
         md = (C.c_int32 * steps)(*[int(x) for x in modes])
         n_v = Vt.shape[1] if Vt is not None else 0
         ldv = Vt.stride(0) if Vt is not None else 0
-        hip_check(hip_lib().svdj_block_steps(
-            dtype_code(At.dtype), W, m_pad, _ptr(At), At.stride(0), _ptr(Vt), n_v, ldv,
-            _ptr(D), _ptr(pairs), P, steps, md, float(tol), tol_mode_code(tol_mode),
-            int(max_inner), _ptr(ws), ws.numel(), _ptr(metric),
-            mma_code(mma, At.dtype) | (STEPS_GRAM2 if gram_parts == 2 else 0)
-            | (STEPS_SHARED_GPU if shared_gpu else 0), _stream(At)), "block_steps")
+        flags = (mma_code(mma, At.dtype) | (STEPS_GRAM2 if gram_parts == 2 else 0)
+                 | (STEPS_SHARED_GPU if shared_gpu else 0))
+        head = (dtype_code(At.dtype), W, m_pad, _ptr(At), At.stride(0), _ptr(Vt), n_v, ldv,
+                _ptr(D), _ptr(pairs), P, steps, md, float(tol), tol_mode_code(tol_mode),
+                int(max_inner), _ptr(ws), ws.numel(), _ptr(metric))
+        if group_blocks is None:
+            hip_check(hip_lib().svdj_block_steps(*head, flags, _stream(At)), "block_steps")
+        else:
+            hip_check(hip_lib().svdj_block_steps_grouped(*head, int(group_blocks), flags,
+                                                         _stream(At)), "block_steps_grouped")
+    elif group_blocks:
+        # the emulation per group: a group's pairs with its own floor, into its own row
+        for s in range(steps):
+            grp = torch.div(pairs[s][:, 0], group_blocks, rounding_mode="floor")
+            for g in torch.unique(grp).tolist():
+                row = metric[g]
+                stats = {"smax": 0.0}
+                mx, nrot = ref.block_step(At[:, :m_pad], Vt, D, pairs[s][grp == g], W,
+                                          modes[s] == STEP_FULL, tol, max_inner,
+                                          tol_mode=tol_mode_code(tol_mode), floor=float(row[2]),
+                                          order=_EVD_ORDER.get(modes[s], "cyclic"), stats=stats)
+                row[0] = max(float(row[0]), mx)
+                row[1] += nrot
+                row[3] = max(float(row[3]), stats["smax"])
+                row[4] += stats.get("ncols", 0)
     else:
         for s in range(steps):
             if modes[s] == STEP_QUAD_SECOND:  # done with the quad's first step
@@ -613,6 +666,80 @@ def block_solve(At, Vt, D, m_pad, W, tol, max_inner, max_sweeps, mma="native",
     return len(hist), hist
 
 
+# ------------------------------------------------- batched path, block engine
+def stack_pack(A3: torch.Tensor, m_pad: int, ncols: int, n_v: int, want_v: bool):
+    """The batch ``A3`` (B, m, n), m >= n, stacked for the block kernels
+    (csrc/hip/batched_block.hip svdj_stack_pack; torch operations on the CPU):
+    returns (At (B ncols, m_pad), Vt (B ncols, n_v) or None, D (B ncols,),
+    metric :func:`new_metric` with B rows).  Matrix b's column j is row
+    b ncols + j of At, pad rows and columns zero; Vt holds an identity block per
+    matrix; D the squared column norms; every metric row its matrix's own
+    floor (:func:`norm_floor` of m_pad and the matrix's largest D)."""
+    B, m, n = A3.shape
+    dev, dt = A3.device, A3.dtype
+    metric = new_metric(dev, groups=B)
+    if A3.is_cuda:
+        At = torch.empty(B * ncols, m_pad, dtype=dt, device=dev)
+        Vt = torch.empty(B * ncols, n_v, dtype=dt, device=dev) if want_v else None
+        D = torch.empty(B * ncols, dtype=dt, device=dev)
+        hip_check(hip_lib().svdj_stack_pack(
+            dtype_code(dt), B, m, n, _ptr(A3), A3.stride(0), A3.stride(1), A3.stride(2), m_pad,
+            ncols, _ptr(At), m_pad, _ptr(Vt), n_v, n_v, _ptr(D), _ptr(metric), _stream(A3)),
+            "stack_pack")
+        return At, Vt, D, metric
+    At = torch.zeros(B, ncols, m_pad, dtype=dt)
+    At[:, :n, :m] = A3.transpose(1, 2)
+    At = At.reshape(B * ncols, m_pad)
+    Vt = None
+    if want_v:
+        Vt = torch.zeros(B, ncols, n_v, dtype=dt)
+        idx = torch.arange(ncols)
+        Vt[:, idx, idx] = 1
+        Vt = Vt.reshape(B * ncols, n_v)
+    D = ref.col_norms2(At)
+    dmax = D.reshape(B, ncols).amax(1).tolist()
+    for b in range(B):
+        metric[b, 2] = norm_floor(dt, m_pad, dmax[b])
+    return At, Vt, D, metric
+
+
+def stack_finalize(At, Vt, B: int, m: int, n: int, m_pad: int, ncols: int, want_u: bool,
+                   want_v: bool):
+    """Sigma, U and V of a stacked solve (svdj_stack_finalize; torch operations
+    on the CPU): returns (U (B, m, n) or None, S (B, n), V (B, n, n) or None),
+    sigma the fp64 column norm, U's columns divided by it (a zero sigma leaves
+    the column as it is)."""
+    dev, dt = At.device, At.dtype
+    if At.is_cuda:
+        U = torch.empty(B, m, n, dtype=dt, device=dev) if want_u else None
+        S = torch.empty(B, n, dtype=dt, device=dev)
+        V = torch.empty(B, n, n, dtype=dt, device=dev) if want_v else None
+        n_v = Vt.shape[1] if Vt is not None else 0
+        hip_check(hip_lib().svdj_stack_finalize(
+            dtype_code(dt), B, m, n, m_pad, ncols, _ptr(At), At.stride(0), _ptr(Vt), n_v,
+            Vt.stride(0) if Vt is not None else 0, _ptr(U), _ptr(S), _ptr(V), int(want_u),
+            _stream(At)), "stack_finalize")
+        return U, S, V
+    sig = ref.finalize(At[:, :m_pad], want_u)
+    A3 = At.reshape(B, ncols, -1)
+    U = A3[:, :n, :m].transpose(1, 2).contiguous() if want_u else None
+    V = Vt.reshape(B, ncols, -1)[:, :n, :n].transpose(1, 2).contiguous() if want_v else None
+    return U, sig.reshape(B, ncols)[:, :n].contiguous(), V
+
+
+def stack_bytes(dtype: torch.dtype, W: int, chunk: int, k: int, m_pad: int, n_v: int,
+                want_v: bool, device) -> int:
+    """Bytes a chunk of ``chunk`` stacked matrices of k W-wide blocks takes:
+    the stacked A, the stacked V, and on a GPU svdj_block_workspace_bytes of a
+    step with all its chunk * k / 2 pairs."""
+    esize = 8 if dtype == torch.float64 else 4
+    total = chunk * k * W * (m_pad + (n_v if want_v else 0)) * esize
+    if torch.device(device).type != "cpu":
+        total += int(hip_lib().svdj_block_workspace_bytes(dtype_code(dtype), W, chunk * k // 2,
+                                                          m_pad, 0))
+    return total
+
+
 # --------------------------------------------------------------- batched path
 BATCHED_MAX_N = 64  # csrc/hip/batched.hip kBatchedMaxN
 
@@ -707,7 +834,8 @@ def batched_tall_svd(A: torch.Tensor, tol: float, tol_mode=0, max_sweeps: int = 
 __all__ = [
     "batched_lds_bytes", "batched_threads", "batched_svd", "BATCHED_MAX_N",
     "batched_tall_lds_bytes", "batched_tall_panel_rows", "batched_tall_balanced_rows",
-    "batched_tall_svd",
+    "batched_tall_svd", "stack_pack", "stack_finalize", "stack_bytes", "reset_group_metrics",
+    "read_group_stops",
     "NativeError", "ROW_ALIGN", "SUPPORTED_BLOCK", "INNER_ORDERS", "step_modes", "dtype_code", "new_metric", "reset_metric", "set_norm_floor",
     "METRIC_WORDS", "read_stop", "metric_stop_values", "metric_work", "sweep_converged", "STOP_RULES",
     "read_metric", "set_identity", "col_norms2", "finalize", "scalar_step", "scalar_solve",
